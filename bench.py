@@ -5,10 +5,16 @@ One "step" = one pass of the hot path over one batch: B independent bootsNAND ga
 resident in HBM.  Workload = BASELINE.json configs[1]: batch 1024 per GPU (weak scaling: each
 rank processes its own shard of independent ciphertexts; no collective on the data path).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run does what the headline needs and no more: keys and
+context, W warm-up steps, the K timed steps, the truth table of the timed batch, the line (with the
+`roofline` figures that come out of the timed steps themselves).  --dump-outputs DIR also writes the
+result arrays of the last timed step (a.npy, b.npy: Torus32 words as float64).  Every other leg below
+runs only with --full (and can then be switched off one by one with its own option).
+
+Extra objects (roofline always; its `clock` and `sustained`, and everything after it, with --full):
   roofline     : the dominant kernel (the blind rotation) against the roofline that binds it,
                  fp64 VALU issue: its algorithmic fp64 FLOPs (198 656 per CMux step, FMA = 2,
                  x 500 steps x B) / its average launch time (HIP events the engine records
@@ -95,7 +101,40 @@ def parse():
     ap.add_argument("--multi-only", action="store_true", help=argparse.SUPPRESS)   # the child of run_multi_child
     ap.add_argument("--parity-samples", type=int, default=128,
                     help="outputs of the timed batch compared Torus32-for-Torus32 with the exact oracle")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg: oracle parity of the timed batch, the other batch sizes, "
+                         "strong scaling, the host-pointer path, the circuits, clock and sustained fp64 ceiling, "
+                         "the one-process multi-device leg, the CPU baseline (each still has its own off switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result arrays of the last timed step to DIR/a.npy ((B, 500)) and DIR/b.npy "
+                         "((B,)), Torus32 words as float64 (a seeded sample of the rows above 64 MB)")
+    args = ap.parse_args()
+    if not args.full:   # a plain run: the headline only
+        args.extra_batches = args.strong_batch = args.host_batches = "none"
+        args.no_circuits = args.no_cpu_baseline = args.no_clock = args.no_ceiling = args.no_multi = True
+        args.parity_samples = 0
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, out, rank):
+    """--dump-outputs: what a caller of the timed path receives from its last step, the LWE
+    results (a[B][500], b[B]) read back from the device, as float64 (every Torus32 word exact).
+    Above the size limit a fixed seeded sample of the rows, in ascending order, plus their indices."""
+    os.makedirs(path, exist_ok=True)
+    a, b = out
+    sfx = "" if rank == 0 else f".rank{rank}"
+    row_bytes = (a.shape[1] + 1) * 8
+    room = DUMP_LIMIT_BYTES - 4096   # the .npy headers
+    if a.shape[0] * row_bytes > room:
+        keep = room // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(64).choice(a.shape[0], keep, replace=False))
+        a, b = a[rows], b[rows]
+        np.save(os.path.join(path, f"rows{sfx}.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, f"a{sfx}.npy"), a.astype(np.float64))
+    np.save(os.path.join(path, f"b{sfx}.npy"), b.astype(np.float64))
 
 
 # ------------------------------------------------------------------------------- CPU side
@@ -610,7 +649,9 @@ def main():
     B = args.batch
     elapsed, prof, truth_ok, main_step, rec = timed(B, args.steps, args.warmup, profile=True)
     local_ms_per_step = local_el[0] / args.steps * 1e3
-    parity = headline_parity(K, args.gate, rec, args.parity_samples, rank, world, red_dev)
+    if args.dump_outputs and rec["outputs"] is not None:
+        dump_outputs(args.dump_outputs, rec["outputs"], rank)
+    parity = headline_parity(K, args.gate, rec, args.parity_samples, rank, world, red_dev) if args.full else {}
 
     br_ms = prof["br_ms"] / max(1, prof["br_launches"])
     ks_ms = prof["ks_ms"] / max(1, prof["ks_launches"])
@@ -662,10 +703,12 @@ def main():
                    "parallelism": f"shard{world} (independent ciphertexts, no collective)"},
         "roofline": roof,
         "truth_table_ok": truth_ok,
-        "parity": parity,
         "kernels": rec["kernels"],
         "engine": T.version(),
+        "full": args.full,
     }
+    if args.full:
+        line["parity"] = parity
 
     # the metric's other batch sizes (per GPU, weak scaling like the headline)
     extras = {}

@@ -15,7 +15,9 @@ if [ ! -d "$REF" ]; then echo "reference not present at $REF; skipping callers b
 if [ ! -f "$LIBDIR/libtfhe_amd.so" ]; then echo "build libtfhe_amd.so first" >&2; exit 1; fi
 mkdir -p "$OUT"
 INC="-I$REPO/include -I$REPO -I$REF"
-LINK="-L$LIBDIR -ltfhe_amd -Wl,-rpath,$LIBDIR"
+# run path relative to the binaries ($OUT = oracle/_ref/callers), as tests/callers/Makefile:
+# the binaries keep finding the library when the tree is moved or copied to another machine
+LINK="-L$LIBDIR -ltfhe_amd -Wl,-rpath,\$ORIGIN/../../../cpu-gpu-tfhe_amd/lib"
 g++ -std=c++11 -O2 $INC "$REF/main.cpp" -o "$OUT/main" $LINK -lgomp
 g++ -std=c++11 -O2 -fopenmp $INC "$REF/cloud.cpp" "$REF/Cipher.cpp" -o "$OUT/cloud" $LINK
 g++ -std=c++11 -O2 -fopenmp $INC "$REPO/tests/callers/cipher_ops.cpp" "$REF/Cipher.cpp" -o "$OUT/cipher_ops" $LINK

@@ -13,7 +13,7 @@ for n in "$@"; do
     *) lib=cpu-gpu-tfhe_amd/variants/$n/libtfhe_amd.so ;;
   esac
   log=gpurun_out/ab_${n}_${AB_BATCH:-1024}_$rep.log
-  TFHE_AMD_LIB=$lib timeout -k 10 200 python bench.py --steps ${AB_STEPS:-5} --warmup ${AB_WARMUP:-1} \
+  TFHE_AMD_LIB=$lib timeout -k 10 200 python bench.py --full --steps ${AB_STEPS:-5} --warmup ${AB_WARMUP:-1} \
       --batch ${AB_BATCH:-1024} --no-cpu-baseline --no-clock --no-ceiling --no-circuits --extra-batches none \
       --strong-batch none --host-batches none > $log 2>&1
   rc=$?; [ $rc -ne 0 ] && { echo "$n rc=$rc"; tail -5 $log; exit $rc; }

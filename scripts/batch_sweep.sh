@@ -5,7 +5,7 @@ set -u
 TAG=${1:-sweep}
 mkdir -p gpurun_out
 for b in ${BATCHES:-1 64 256 512 768 1024 2048 4096}; do
-  timeout -k 10 200 python bench.py --batch $b --steps 20 --warmup 10 --no-cpu-baseline --no-clock --no-ceiling \
+  timeout -k 10 200 python bench.py --full --batch $b --steps 20 --warmup 10 --no-cpu-baseline --no-clock --no-ceiling \
       --extra-batches none --strong-batch 0 --parity-samples 16 > gpurun_out/${TAG}_$b.json 2>/dev/null || exit 3
   python3 -c "
 import json

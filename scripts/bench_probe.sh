@@ -1,7 +1,9 @@
 #!/usr/bin/env bash
-# GPU box: the default bench line plus the raw amd-smi clock JSON its clock sampler parses.
+# GPU box: the full bench line plus the raw amd-smi clock JSON its clock sampler parses.
+#   OUT=<directory> bash scripts/bench_probe.sh      (default: bench_out/)
 set -u
-mkdir -p gpurun_out
-(amd-smi metric -g 0 --clock --json > gpurun_out/amdsmi_clock.json 2>&1 || true)
-timeout -k 10 300 python bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
-rc=$?; tail -c 3000 gpurun_out/bench_default.json; tail -5 gpurun_out/bench_default.err; exit $rc
+O=${OUT:-bench_out}
+mkdir -p "$O"
+(amd-smi metric -g 0 --clock --json > $O/amdsmi_clock.json 2>&1 || true)
+timeout -k 10 300 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+rc=$?; tail -c 3000 $O/bench_default.json; tail -5 $O/bench_default.err; exit $rc

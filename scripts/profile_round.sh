@@ -6,7 +6,7 @@
 # rocprof durations of the headline's timed launches; scripts/pmc_summary.py turns the FETCH /
 # WRITE passes of the same command into profiles/pmc_summary.json.
 #   bash scripts/profile_round.sh <tag> [bench|headline] [extra bench args...]
-#     bench    : the driver's command, every leg (default)
+#     bench    : the driver's command with --full, every leg (default)
 #     headline : only the B = 1024 headline (legs, CPU baseline, clock, ceiling off): quicker PMC
 set -u
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -19,7 +19,7 @@ cd /tmp && export TMPDIR=/tmp
 if [ "$MODE" = headline ]; then
   BENCH="$R/bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-clock --no-ceiling --extra-batches none --strong-batch 0 --host-batches none $*"
 else
-  BENCH="$R/bench.py --gpus 1 --steps 20 --warmup 5 $*"
+  BENCH="$R/bench.py --gpus 1 --steps 20 --warmup 5 --full $*"
 fi
 # PMC passes: the same command with --no-clock — amd-smi is a python script started through
 # /usr/bin/env, an exec the box refuses once the PMC profiler's preload has initialised the GPU

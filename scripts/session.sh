@@ -6,7 +6,7 @@
 #   tests            the whole -m gpu suite                  -> <tag>/gpu_tests.txt
 #   tests:<args>     pytest on a subset, e.g. tests:tests/test_gpu_parity.py,-k,paired
 #   smoke            __graft_entry__.smoke()                  -> <tag>/smoke.txt
-#   bench[:name]     the driver's bench command               -> <tag>/bench_<name>.json
+#   bench[:name]     the driver's bench command with --full   -> <tag>/bench_<name>.json
 #   profile          scripts/profile_round.sh <tag> bench (rocprofv3 trace + PMC passes of that command)
 #   profile_headline the same, headline leg only
 #   gloo2            two ranks sharing this GPU over gloo (the N > 1 path)  -> <tag>/bench_2ranks.json
@@ -29,10 +29,10 @@ for s in "$@"; do
     tests:*) a="${s#tests:}"; c="timeout -k 10 600 python -u -m pytest ${a//,/ } -m gpu -x -v --timeout 300 --timeout-method thread >> $O/gpu_tests_subset.txt 2>&1" ;;
     smoke) c="timeout -k 10 300 python -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.txt 2>&1" ;;
     bench|bench:*) n="${s#bench}"; n="${n#:}"; n="${n:-default}"
-      c="timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_$n.json 2> $O/bench_$n.err" ;;
+      c="timeout -k 10 400 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_$n.json 2> $O/bench_$n.err" ;;
     profile) c="timeout -k 10 1150 bash scripts/profile_round.sh $TAG bench > $O/profile.txt 2>&1" ;;
     profile_headline) c="timeout -k 10 900 bash scripts/profile_round.sh $TAG headline > $O/profile.txt 2>&1" ;;
-    gloo2) c="TFHE_AMD_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 3 --host-batches none > $O/bench_2ranks.json 2> $O/bench_2ranks.err" ;;
+    gloo2) c="TFHE_AMD_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 10 --warmup 3 --full --host-batches none > $O/bench_2ranks.json 2> $O/bench_2ranks.err" ;;
     sweep:*) b="${s#sweep:}"; c="BATCHES='${b//,/ }' timeout -k 10 600 bash scripts/batch_sweep.sh $TAG/sweep > /dev/null 2>&1" ;;
     host:*) b="${s#host:}"; c="timeout -k 10 300 python scripts/host_path_rate.py ${b//,/ } >> $O/host_path.jsonl 2>&1" ;;
     tier1:*) a="${s#tier1:}"; c="timeout -k 10 300 tests/callers/_bin/tier1_rate ${a//,/ } >> $O/tier1_rate.json 2>&1" ;;

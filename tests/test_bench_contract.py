@@ -39,7 +39,7 @@ def test_committed_pmc_summary_is_the_headlines():
 
 @pytest.mark.gpu
 def test_bench_line_fields():
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--full",
            "--no-clock", "--no-ceiling", "--extra-batches", "none", "--strong-batch", "0", "--host-batches", "none",
            "--no-circuits", "--cpu-seconds", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=REPO)
@@ -69,6 +69,33 @@ def test_bench_line_fields():
         assert k in cb, k
     assert cb["kind"] in ("port", "reference") and cb["value"] > 0
     assert d["truth_table_ok"] is True and d["parity"]["mismatches"] == 0
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_only_and_dumps_outputs(tmp_path, keyset):
+    """Without --full the line carries the headline (and the roofline its timed steps give) and
+    none of the other legs; --dump-outputs writes the last timed step's results, a (B, 500) and
+    b (B,) as float64 Torus32 words, which decrypt to the NAND of the bench's seeded input bits."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=REPO)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    d = _line(r.stdout)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["full"] is False and d["truth_table_ok"] is True
+    assert abs(d["value"] - 1024 / (d["ms_per_step"] / 1e3)) / d["value"] < 1e-6
+    for k in ("parity", "batches", "strong", "host_path", "host_path_pinned", "circuits", "cpu_baseline",
+              "gpu_over_cpu", "one_process_multi_device"):
+        assert k not in d, k
+    assert "clock" not in d["roofline"] and "sustained" not in d["roofline"]
+    a, b = np.load(tmp_path / "out" / "a.npy"), np.load(tmp_path / "out" / "b.npy")
+    assert a.dtype == np.float64 and b.dtype == np.float64 and a.shape == (1024, 500) and b.shape == (1024,)
+    assert np.array_equal(a, np.rint(a)) and np.abs(a).max() <= 2.0**31 and np.abs(b).max() <= 2.0**31
+    rng = np.random.default_rng(1000)                      # bench.py's rank-0 stream: x, y drawn first
+    x, y = rng.integers(0, 2, 1024), rng.integers(0, 2, 1024)
+    assert np.array_equal(keyset.decrypt(a.astype(np.int64), b.astype(np.int64)), 1 - (x & y))
 
 
 @pytest.mark.gpu

@@ -89,6 +89,23 @@ def test_config3_ripple_add_32bit_circuit(ctx, keyset, rng):
         assert np.array_equal(T.int_of([got[w] for w in s + [co]]), x[:B] + y[:B])
 
 
+def _callers_env():
+    """Environment for the binaries in oracle/_ref/callers: their run path finds libtfhe_amd.so
+    relative to the directory they were built into; this tree's library directory is named as well,
+    so that binaries built in another checkout, or reached through a linked oracle/_ref, load the
+    library under test."""
+    lib = os.path.join(REPO, "cpu-gpu-tfhe_amd", "lib")
+    old = os.environ.get("LD_LIBRARY_PATH")
+    return dict(os.environ, LD_LIBRARY_PATH=lib + (os.pathsep + old if old else ""))
+
+
+def _run_main(tmp_path, a, b):
+    """The reference's client (main.cpp): key generation, encryption of a and b, the three files."""
+    r = subprocess.run([os.path.join(CALLERS, "main"), str(a), str(b)], cwd=tmp_path,
+                       env=_callers_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+
+
 def _callers_built():
     return all(os.path.exists(os.path.join(CALLERS, f)) for f in ("main", "cipher_ops"))
 
@@ -99,11 +116,10 @@ def test_config3_cipher_operator_plus_32bit(tmp_path):
     against libtfhe_amd and run on the MI355X."""
     if not _callers_built():
         pytest.skip("oracle/_ref/callers not built (needs the reference sources at build time)")
-    subprocess.run([os.path.join(CALLERS, "main"), "1", "2"], cwd=tmp_path, check=True, timeout=300,
-                   capture_output=True)
+    _run_main(tmp_path, 1, 2)
     for av, bv in ((3000000000, 1234567890), (0xFFFFFFFF, 1)):
         r = subprocess.run([os.path.join(CALLERS, "cipher_ops"), "add32", str(av), str(bv)], cwd=tmp_path,
-                           capture_output=True, text=True, timeout=600)
+                           env=_callers_env(), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         out = json.loads(r.stdout.strip().splitlines()[-1])
         assert out["a"] == av and out["b"] == bv
@@ -128,13 +144,12 @@ def test_cipher_operator_times_16bit_openmp(tmp_path):
     variation."""
     if not (_callers_built() and os.path.exists(os.path.join(CALLERS, "cipher_ops_par"))):
         pytest.skip("oracle/_ref/callers not built (needs the reference sources at build time)")
-    subprocess.run([os.path.join(CALLERS, "main"), "1", "2"], cwd=tmp_path, check=True, timeout=300,
-                   capture_output=True)
+    _run_main(tmp_path, 1, 2)
     av, bv = 0xBEEF, 0xFACE
     res = {}
     for exe, th in (("cipher_ops", 1), ("cipher_ops_par", 4), ("cipher_ops_par", 16)):
         r = subprocess.run([os.path.join(CALLERS, exe), "mul16", str(av), str(bv), str(th)], cwd=tmp_path,
-                           capture_output=True, text=True, timeout=600)
+                           env=_callers_env(), capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         out = json.loads(r.stdout.strip().splitlines()[-1])
         assert out["prod"] == av * bv, out

@@ -206,6 +206,23 @@ def test_good_file_loads_in_child(files):
 
 # ---------------------------------------------------------------- the reference's callers
 
+def _callers_env():
+    """Environment for the binaries in oracle/_ref/callers: their run path finds libtfhe_amd.so
+    relative to the directory they were built into; this tree's library directory is named as well,
+    so that binaries built in another checkout, or reached through a linked oracle/_ref, load the
+    library under test."""
+    lib = os.path.join(REPO, "cpu-gpu-tfhe_amd", "lib")
+    old = os.environ.get("LD_LIBRARY_PATH")
+    return dict(os.environ, LD_LIBRARY_PATH=lib + (os.pathsep + old if old else ""))
+
+
+def _run_main(tmp_path, a, b):
+    """The reference's client (main.cpp): key generation, encryption of a and b, the three files."""
+    r = subprocess.run([os.path.join(CALLERS, "main"), str(a), str(b)], cwd=tmp_path,
+                       env=_callers_env(), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+
+
 def _callers_built():
     return all(os.path.exists(os.path.join(CALLERS, b)) for b in ("main", "cloud", "cipher_ops"))
 
@@ -224,8 +241,7 @@ def test_reference_main_writes_readable_files(tmp_path):
     export secret.key / cloud.key / cloud.data); read everything back through our loader."""
     if not _callers_built():
         subprocess.check_call(["bash", os.path.join(REPO, "oracle", "build_callers.sh")])
-    subprocess.run([os.path.join(CALLERS, "main"), "10", "2"], cwd=tmp_path, check=True, timeout=300,
-                   capture_output=True)
+    _run_main(tmp_path, 10, 2)
     K = T.SecretKeyset(path=str(tmp_path / "secret.key"))
     try:
         a, b, _ = T.read_ciphertexts(str(tmp_path / "cloud.data"), K.params, 32)
@@ -249,9 +265,9 @@ def test_reference_callers_gpu(tmp_path):
     TFHE API, on keys and ciphertexts from the reference's main.cpp."""
     if not _callers_built():
         pytest.skip("oracle/_ref/callers not built (needs the reference sources at build time)")
-    subprocess.run([os.path.join(CALLERS, "main"), "1234", "567"], cwd=tmp_path, check=True, timeout=300,
-                   capture_output=True)
-    r = subprocess.run([os.path.join(CALLERS, "cipher_ops")], cwd=tmp_path, capture_output=True, text=True,
+    _run_main(tmp_path, 1234, 567)
+    r = subprocess.run([os.path.join(CALLERS, "cipher_ops")], cwd=tmp_path, env=_callers_env(),
+                       capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
