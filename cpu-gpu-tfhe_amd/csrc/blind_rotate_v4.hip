@@ -50,7 +50,7 @@ __device__ __forceinline__ void e_store(uint32_t *E, int j, uint32_t v) {
 // The exact external-product coefficient c has |c| < 2^52 << q0 q1 / 2, so the lift
 // x0 + q0 tc with tc = (x1 - x0) q0^-1 mod q1 taken in (-q1/2, q1/2] equals c.
 __device__ __forceinline__ uint32_t crt_lazy(uint32_t x0, uint32_t x1, uint32_t h, uint32_t hp) {
-    const uint32_t d = x1 + 3u * kQ1 - x0;                      // (q1, 5 q1)
+    const uint32_t d = x1 + 3u * kQ1 - x0;                      // (3 q1 - 2 q0, 5 q1), > 0
     const uint32_t t0 = shoup_lazy(d, h, hp, 0u - kQ1);         // [0, 2 q1)
     const uint32_t t = umin32(t0, t0 - kQ1);                    // [0, q1)
     const uint32_t tc = t > (kQ1 - 1) / 2 ? t - kQ1 : t;

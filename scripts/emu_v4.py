@@ -80,7 +80,8 @@ def tw_inv(s, stage, p):
 
 def inv_v4(Y, s):
     """Y in layout C as [L][r] (slot k = 16L + r): DIT stages 0..3 (C), 4..5 (B), 6..9 (A),
-    post-twist; returns layout A values (n = L + 64 r), lazy [0, 2q)."""
+    post-twist; returns (layout A values (n = L + 64 r), lazy [0, 2q); the largest value before
+    the post-twist)."""
     q = Q[s]
     x = [row[:] for row in Y]
     for st in range(4):                      # layout C, uniform twiddles, p = r mod 2^st
@@ -121,6 +122,8 @@ def inv_v4(Y, s):
                 p = L + 64 * g
                 assert jA(L, r) % (1 << st) == p and jA(L, r + d) == jA(L, r) + (1 << st)
                 x[L][r], x[L][r + d] = bf_ct(x[L][r], x[L][r + d], tw_inv(s, st, p), q, None)
+    top = max(max(row) for row in x)         # the inverse's lazy output, before the post-twist
+    assert top < 31.75 * q
     for L in range(64):                      # post-twist psi^-n, n = L + 64 r (Shoup lazy, positive)
         for r in range(16):
             n = L + 64 * r
@@ -131,7 +134,7 @@ def inv_v4(Y, s):
             t = (y * w - qh * q) & M32
             assert t < 2 * q and t % q == y * w % q
             x[L][r] = t
-    return x
+    return x, top
 
 
 def crt_lazy(x0, x1):
@@ -147,11 +150,16 @@ def crt_lazy(x0, x1):
     return (x0 + q0 * tc) & M32
 
 
-def main():
-    rnd = random.Random(1)
-    # 4 digit polys in [-512, 511] and 4 BK rows (Torus32), one output poly c
-    D = [[rnd.randrange(-512, 512) for _ in range(N)] for _ in range(4)]
-    Bk = [[rnd.randrange(0, 2**32) for _ in range(N)] for _ in range(4)]
+def signed_residue(v, q):
+    """k_bk_to_ntt's reduction of one key word: C's truncating v % q, then r < 0 ? r + q : r."""
+    r = abs(v) % q
+    if v < 0:
+        r = -r
+    return r + q if r < 0 else r
+
+
+def exact_product(D, Bk):
+    """sum_p D[p] * Bk[p] mod X^N + 1 over the integers (no reduction)"""
     exact = [0] * N
     for p in range(4):
         for i in range(N):
@@ -165,15 +173,28 @@ def main():
                     exact[k - N] -= v
                 else:
                     exact[k] += v
-    exact = [e & M32 for e in exact]
+    return exact
+
+
+def external_product(D, Bk):
+    """One output polynomial of the v4 external product: 4 digit polys D[p] in [-512, 511] and 4 key
+    rows Bk[p], each word the integer value the kernel reads (an int32, so -2^31 .. 2^31 - 1),
+    reduced as k_bk_to_ntt does.  Returns (c mod 2^32 per coefficient, peaks) where peaks holds the
+    largest lazy value of each stage as a multiple of q: "fwd" (forward NTT output, bound 22),
+    "mac" (REDC output, bound 3.75) and "inv" (inverse output before the post-twist, bound 31.75).
+    Every bound the kernel's comments state is asserted on the way."""
+    peaks = {"fwd": 0.0, "mac": 0.0, "inv": 0.0}
     outs = []
     for s in range(2):
         q = Q[s]
         Dh = [fwd_ntt([(d + q) for d in D[p]], s) for p in range(4)]            # lifted digits
-        assert max(max(v) for v in Dh) < 22 * q
+        top = max(max(v) for v in Dh)
+        assert top < 22 * q
+        peaks["fwd"] = max(peaks["fwd"], top / q)
         ninv = pow(N, q - 2, q)
         R = (1 << 32) % q
-        Bh = [[(v * ninv % q) * R % q for v in fwd_ntt([b % q for b in Bk[p]], s)] for p in range(4)]
+        Bh = [[(v * ninv % q) * R % q for v in fwd_ntt([signed_residue(b, q) for b in Bk[p]], s)]
+              for p in range(4)]
         qinv_neg = (-pow(q, -1, 1 << 32)) & M32
         Y = []
         for k in range(N):
@@ -183,12 +204,26 @@ def main():
             t = (xx + m * q) >> 32
             assert t < 3.75 * q + 1
             Y.append(t)
+        peaks["mac"] = max(peaks["mac"], max(Y) / q)
         YC = [[Y[jC(L, r)] for r in range(16)] for L in range(64)]
-        outs.append(inv_v4(YC, s))
+        x, top = inv_v4(YC, s)
+        peaks["inv"] = max(peaks["inv"], top / q)
+        outs.append(x)
     got = [0] * N
     for L in range(64):
         for r in range(16):
             got[L + 64 * r] = crt_lazy(outs[0][L][r], outs[1][L][r])
+    return got, peaks
+
+
+def main():
+    rnd = random.Random(1)
+    # 4 digit polys in [-512, 511] and 4 BK rows (Torus32 as int32), one output poly c
+    D = [[rnd.randrange(-512, 512) for _ in range(N)] for _ in range(4)]
+    Bk = [[rnd.randrange(-2**31, 2**31) for _ in range(N)] for _ in range(4)]
+    exact = [e & M32 for e in exact_product(D, Bk)]
+    got, peaks = external_product(D, Bk)
+    print("peaks (multiples of q): forward %.2f, MAC %.2f, inverse %.2f" % (peaks["fwd"], peaks["mac"], peaks["inv"]))
     bad = sum(1 for a, b in zip(got, exact) if a != b)
     print("mismatches:", bad)
     assert bad == 0
