@@ -155,9 +155,13 @@ struct RowTerms {
     const int32_t *xa, *xb, *ya, *yb, *za, *zb;   // a rows (kn) and b words; y/z may be null
 };
 
-// prologue + modswitch + 500 CMux steps + extraction of one ciphertext into (ua, *ub)
+// prologue + modswitch + 500 CMux steps + extraction of one ciphertext into (ua, *ub).
+// LUT (programmable bootstrap, compile-time): the accumulator starts from the test vector tv [kN]
+// in device memory; tv = null (a constant row beside LUT rows) keeps the constant (mu, ..., mu)
+template <bool LUT = false>
 __device__ __forceinline__ void br_v4_body(V4Shared &sh, const V4Args &g, const RowTerms &t, int32_t mu,
-                                           int32_t *__restrict__ ua, int32_t *__restrict__ ub) {
+                                           int32_t *__restrict__ ua, int32_t *__restrict__ ub,
+                                           const int32_t *__restrict__ tv = nullptr) {
     const int tid = threadIdx.x;
     const int s = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = tid & 63;
@@ -175,7 +179,13 @@ __device__ __forceinline__ void br_v4_body(V4Shared &sh, const V4Args &g, const 
         sh.barb = modswitch_2N(xb);
     }
     __syncthreads();
-    {   // ACC = (0, X^{2N - barb} (mu, ..., mu)) (:1427-1431), as its periodic extension
+    if (LUT && tv) {   // ACC = (0, X^{2N - barb} tv) as its periodic extension (modarith.h lut_coeff)
+        const int e = (k2N - sh.barb) & (k2N - 1);
+        for (int k = tid; k < kExt; k += kV4Threads) {
+            sh.E[0][k] = 0;
+            sh.E[1][k] = lut_coeff(tv, k, e);
+        }
+    } else {   // ACC = (0, X^{2N - barb} (mu, ..., mu)) (:1427-1431), as its periodic extension
         const int e = (k2N - sh.barb) & (k2N - 1);
         for (int k = tid; k < kExt; k += kV4Threads) {
             sh.E[0][k] = 0;
@@ -216,7 +226,7 @@ __device__ __forceinline__ bool guard_skip(const V4Guard &gd, size_t slot) {
 // (tfhe_amd_select_kernel(4): 256 VGPRs, 27 spilled), 1 for the guard launch (284 VGPRs, no scratch: a
 // kernel with a private segment costs ~12 us more per dispatch even when every workgroup exits
 // at once)
-template <int MINW>
+template <int MINW, bool LUT = false>
 __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4(V4Args g, int B, int total, BrInput in0,
                                                                 BrInput in1, int32_t mu,
                                                                 int32_t *__restrict__ u_a,
@@ -235,13 +245,17 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4(V4Args g, 
         t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
         t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
         t.za = nullptr; t.zb = nullptr;
-        br_v4_body(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct);
+        if constexpr (LUT)
+            br_v4_body<true>(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct,
+                             lut_table(in.tv, in.lut_index, in.n_lut, idx));
+        else
+            br_v4_body(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct);
     }
 }
 
 // circuit level: flat slot r B + k (row r, instance k < B), grid-stride as the gate kernel;
 // wires are [W][B] ciphertexts, the extracted sample of (r, k) goes to u slot r B + k
-template <int MINW>
+template <int MINW, bool LUT = false>
 __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4_rows(V4Args g, int B, long total,
                                                                      const CircRow *__restrict__ rows,
                                                                      const int32_t *__restrict__ wa,
@@ -267,7 +281,13 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4_rows(V4Arg
         wire(row.x, t.xa, t.xb);
         wire(row.y, t.ya, t.yb);
         wire(row.z, t.za, t.zb);
-        br_v4_body(sh, g, t, mu, u_a + (size_t)slot * kN, u_b + slot);
+        if constexpr (LUT) {
+            // a LUT row's test vector lies row.lut words after its own record (engine.h CircRow)
+            const int32_t *tv = row.lut ? reinterpret_cast<const int32_t *>(rows + r) + row.lut : nullptr;
+            br_v4_body<true>(sh, g, t, mu, u_a + (size_t)slot * kN, u_b + slot, tv);
+        } else {
+            br_v4_body(sh, g, t, mu, u_a + (size_t)slot * kN, u_b + slot);
+        }
     }
 }
 
@@ -374,6 +394,20 @@ hipError_t launch_blind_rotate_v4(const DeviceKey &key, int B, int halves, const
     const int total = B * halves;
     // guard mode: 256 workgroups scan the flags (B = 1024: 15 -> ~4 us per launch)
     const int grid = gd.flags && total > kGuardGrid ? kGuardGrid : total;
+    // programmable bootstrap: every half carries its tables (n_lut >= 1), or none does; the guard
+    // launch recomputes a flagged ciphertext from the same table
+    const bool lut = in[0].tv != nullptr;
+    if (lut != (in1.tv != nullptr) || (lut && (in[0].n_lut <= 0 || in1.n_lut <= 0))) return hipErrorInvalidValue;
+    if (lut) {
+        trace_kernel(gd.flags ? "k_blind_rotate_v4(lut+guard)" : "k_blind_rotate_v4(lut)");
+        if (gd.flags)
+            hipLaunchKernelGGL((k_blind_rotate_v4<1, true>), dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B, total,
+                               in[0], in1, mu, u_a, u_b, gd);
+        else
+            hipLaunchKernelGGL((k_blind_rotate_v4<2, true>), dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B, total,
+                               in[0], in1, mu, u_a, u_b, gd);
+        return hipGetLastError();
+    }
     trace_kernel(gd.flags ? "k_blind_rotate_v4(guard)" : "k_blind_rotate_v4");
     if (gd.flags)
         hipLaunchKernelGGL(k_blind_rotate_v4<1>, dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B, total, in[0],
@@ -392,6 +426,16 @@ hipError_t launch_blind_rotate_v4_rows(const DeviceKey &key, int B, int nrows, c
     const V4Guard gd = v4_guard(guard);
     const long total = (long)B * nrows;
     const long grid = gd.flags && total > kGuardGrid ? kGuardGrid : total < 0x7fffffffL ? total : 0x7fffffffL;
+    if (guard && guard->lut_rows) {   // some row carries a test vector (engine.h Guard)
+        trace_kernel(gd.flags ? "k_blind_rotate_v4_rows(lut+guard)" : "k_blind_rotate_v4_rows(lut)");
+        if (gd.flags)
+            hipLaunchKernelGGL((k_blind_rotate_v4_rows<1, true>), dim3((unsigned)grid), dim3(kV4Threads), 0, s,
+                               v4_args(key), B, total, rows, wa, wb, mu, u_a, u_b, gd);
+        else
+            hipLaunchKernelGGL((k_blind_rotate_v4_rows<2, true>), dim3((unsigned)grid), dim3(kV4Threads), 0, s,
+                               v4_args(key), B, total, rows, wa, wb, mu, u_a, u_b, gd);
+        return hipGetLastError();
+    }
     trace_kernel(gd.flags ? "k_blind_rotate_v4_rows(guard)" : "k_blind_rotate_v4_rows");
     if (gd.flags)
         hipLaunchKernelGGL(k_blind_rotate_v4_rows<1>, dim3((unsigned)grid), dim3(kV4Threads), 0, s, v4_args(key), B,

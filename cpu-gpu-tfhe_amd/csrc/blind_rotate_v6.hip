@@ -366,10 +366,14 @@ __device__ __forceinline__ void cmux_v6(V6Ct &sh, const double2 *shtw, const V6A
 // the workgroup's barriers lock-step both, so neither skips a_i = 0 steps (the identity CMux is
 // exact: zero digits, zero transforms, zero products).  live = false: a padding ciphertext that
 // computes but writes nothing.
-template <int WAVES, bool RREG, int C = 1, bool PS = false>
+// LUT (programmable bootstrap): the accumulator starts from the test vector tv [kN] in device
+// memory instead of the constant (mu, ..., mu); tv = null (a constant row of a rows launch that
+// also holds LUT rows) keeps the arithmetic initialisation.  Compile-time, so the constant
+// instantiations are untouched.
+template <int WAVES, bool RREG, int C = 1, bool PS = false, bool LUT = false>
 __device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args &g, const RowTerms6 &t, int32_t mu,
                                            int32_t *__restrict__ ua, int32_t *__restrict__ ub, size_t slot,
-                                           bool live = true) {
+                                           bool live = true, const int32_t *__restrict__ tv = nullptr) {
     const int tid = threadIdx.x & (kV6Threads - 1);
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = tid & 63;
@@ -401,7 +405,17 @@ __device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args
     __syncthreads();
     // ACC = (0, X^{2N - barb} (mu, ..., mu)) (:1427-1431)
     uint32_t acc[16];
-    {
+    if (LUT && tv) {
+        // ACC = (0, X^{2N - barb} tv) (modarith.h lut_coeff): wave 1 makes 16 loads per lane (64
+        // consecutive words per load, up to the wrap), wave 0 stays zero
+        const int e = (k2N - sh.barb) & (k2N - 1);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0u;
+        if (w == 1) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = lut_coeff(tv, L + 64 * r, e);
+        }
+    } else {
         const int e = (k2N - sh.barb) & (k2N - 1);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
@@ -467,7 +481,7 @@ __device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args
 #endif
 }
 
-template <int WAVES, bool RREG>
+template <int WAVES, bool RREG, bool LUT = false>
 __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6(V6Args g, int B, int base, BrInput in0,
                                                                 BrInput in1, int32_t mu, int32_t *__restrict__ u_a,
                                                                 int32_t *__restrict__ u_b) {
@@ -481,13 +495,17 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6(V6Args g,
     t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
     t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
     t.za = nullptr; t.zb = nullptr;
-    br_v6_body<WAVES, RREG>(sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct);
+    if constexpr (LUT)
+        br_v6_body<WAVES, RREG, 1, false, true>(sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct,
+                                                true, lut_table(in.tv, in.lut_index, in.n_lut, idx));
+    else
+        br_v6_body<WAVES, RREG>(sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct);
 }
 
 // two ciphertexts per workgroup (4 waves): the dispatcher spreads a 4-wave workgroup over the
 // CU's 4 SIMDs, where two 2-wave workgroups sharing a CU land on 3 of them (2, 1, 1, 0 waves;
 // scripts/wave_placement.hip), so at B <= 2 CUs this keeps one wave per SIMD
-template <int WAVES, bool PS = false>
+template <int WAVES, bool PS = false, bool LUT = false>
 __global__ __launch_bounds__(2 * kV6Threads, WAVES) void k_blind_rotate_v6p(V6Args g, int B, int total, int base,
                                                                      BrInput in0, BrInput in1, int32_t mu,
                                                                      int32_t *__restrict__ u_a,
@@ -505,10 +523,15 @@ __global__ __launch_bounds__(2 * kV6Threads, WAVES) void k_blind_rotate_v6p(V6Ar
     t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
     t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
     t.za = nullptr; t.zb = nullptr;
-    br_v6_body<WAVES, true, 2, PS>(sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct, live);
+    // (the padding ciphertext repeats the last live one, table included)
+    if constexpr (LUT)
+        br_v6_body<WAVES, true, 2, PS, true>(sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct,
+                                             live, lut_table(in.tv, in.lut_index, in.n_lut, idx));
+    else
+        br_v6_body<WAVES, true, 2, PS>(sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct, live);
 }
 
-template <int WAVES, bool RREG>
+template <int WAVES, bool RREG, bool LUT = false>
 __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6_rows(V6Args g, int B, long base,
                                                                      const CircRow *__restrict__ rows,
                                                                      const int32_t *__restrict__ wa,
@@ -531,7 +554,13 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6_rows(V6Ar
     wire(row.y, t.ya, t.yb);
     wire(row.z, t.za, t.zb);
     const size_t slot = (size_t)r * B + k;
-    br_v6_body<WAVES, RREG>(sh.ct[0], sh.tw, g, t, mu, u_a + slot * kN, u_b + slot, slot);
+    if constexpr (LUT) {
+        // a LUT row's test vector lies row.lut words after its own record (engine.h CircRow)
+        const int32_t *tv = row.lut ? reinterpret_cast<const int32_t *>(rows + r) + row.lut : nullptr;
+        br_v6_body<WAVES, RREG, 1, false, true>(sh.ct[0], sh.tw, g, t, mu, u_a + slot * kN, u_b + slot, slot, true, tv);
+    } else {
+        br_v6_body<WAVES, RREG>(sh.ct[0], sh.tw, g, t, mu, u_a + slot * kN, u_b + slot, slot);
+    }
 }
 
 template <bool RREG>
@@ -720,9 +749,36 @@ hipError_t launch_blind_rotate_v6(const DeviceKey &key, int B, int halves, const
     if (!key.bk_fft) return hipErrorInvalidValue;
     const BrInput in1 = halves > 1 ? in[1] : in[0];
     const long total = (long)B * halves, chunk = v6_chunk(key);
+    // programmable bootstrap: every half carries its tables (n_lut >= 1), or none does
+    const bool lut = in[0].tv != nullptr;
+    if (lut != (in1.tv != nullptr) || (lut && (in[0].n_lut <= 0 || in1.n_lut <= 0))) return hipErrorInvalidValue;
     for (long base = 0; base < total; base += chunk) {
         const long n = total - base < chunk ? total - base : chunk;
-        if (v6_pair(key, n)) {
+        if (lut) {
+            // the constant path's launch forms, LUT instantiations
+            if (v6_pair(key, n)) {
+                const long wgs = (n + 1) / 2;
+                if (v6p_pairsync() && guard && guard->flags) {
+                    trace_kernel("k_blind_rotate_v6p(lut+paired+reg-rotation+pair-sync)");
+                    hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, true, true>), dim3((unsigned)wgs),
+                                       dim3(2 * kV6Threads), 0, s, v6_args(key, wgs, guard, true), B, (int)total,
+                                       (int)base, in[0], in1, mu, u_a, u_b);
+                } else {
+                    trace_kernel("k_blind_rotate_v6p(lut+paired+reg-rotation)");
+                    hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, false, true>), dim3((unsigned)wgs),
+                                       dim3(2 * kV6Threads), 0, s, v6_args(key, wgs, guard, true), B, (int)total,
+                                       (int)base, in[0], in1, mu, u_a, u_b);
+                }
+            } else if (v6_rreg(key, n)) {
+                trace_kernel("k_blind_rotate_v6(lut+reg-rotation)");
+                hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, true, true>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
+                                   v6_args(key, n, guard), B, (int)base, in[0], in1, mu, u_a, u_b);
+            } else {
+                trace_kernel("k_blind_rotate_v6(lut+lds-rotation)");
+                hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, false, true>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
+                                   v6_args(key, n, guard), B, (int)base, in[0], in1, mu, u_a, u_b);
+            }
+        } else if (v6_pair(key, n)) {
             const long wgs = (n + 1) / 2;
             // the pair sync's bounded poll hands a ciphertext whose partner never arrives to the
             // guard (bad flag -> exact recomputation): only with guard flags to hand it to
@@ -757,6 +813,17 @@ hipError_t launch_blind_rotate_v6_rows(const DeviceKey &key, int B, int nrows, c
     for (long base = 0; base < total; base += chunk) {
         const long n = total - base < chunk ? total - base : chunk;
         if (n > 0x7fffffffL) return hipErrorInvalidValue;
+        if (guard && guard->lut_rows) {   // some row carries a test vector (engine.h Guard)
+            trace_kernel(v6_rreg(key, n) ? "k_blind_rotate_v6_rows(lut+reg-rotation)"
+                                         : "k_blind_rotate_v6_rows(lut+lds-rotation)");
+            if (v6_rreg(key, n))
+                hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, true, true>), dim3((unsigned)n), dim3(kV6Threads), 0,
+                                   s, v6_args(key, n, guard), B, base, rows, wa, wb, mu, u_a, u_b);
+            else
+                hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, false, true>), dim3((unsigned)n), dim3(kV6Threads), 0,
+                                   s, v6_args(key, n, guard), B, base, rows, wa, wb, mu, u_a, u_b);
+            continue;
+        }
         trace_kernel(v6_rreg(key, n) ? "k_blind_rotate_v6_rows(reg-rotation)" : "k_blind_rotate_v6_rows(lds-rotation)");
         if (v6_rreg(key, n))
             hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, true>), dim3((unsigned)n), dim3(kV6Threads), 0, s,

@@ -40,7 +40,9 @@ struct Node {
     int32_t c0;          // lincomb / affine constant
     int32_t s[3];        // lincomb coefficients
     int in[3];           // input wires (-1 = absent)
+    int table = -1;      // programmable-bootstrap node (gate kLutGate): its test vector's table id
 };
+constexpr int kLutGate = -2;   // gate code of a LUT node (tfhe_amd_circuit_node)
 
 struct Affine {          // W = (0, c) + s W[base]; base = -1: the trivial sample (0, c)
     int32_t c, s;
@@ -76,11 +78,14 @@ struct TfheAmdCircuit {
     std::vector<Node> nodes;           // one per wire
     // compiled schedule
     bool compiled = false;
-    struct Level { int row0, nrows, ks0, nks, lin0, nlin; };
+    struct Level { int row0, nrows, ks0, nks, lin0, nlin; bool lut; };   // lut: some row carries a test vector
     std::vector<Level> levels;         // levels[0]: affine nodes over inputs only
     std::vector<CircRow> rows;
     std::vector<CircKs> ks;
     std::vector<CircLin> lin;
+    // programmable-bootstrap test vectors [n][kN]; uploaded behind the level tables, where the LUT
+    // rows find them by a self-relative offset (engine.h CircRow.lut)
+    std::vector<int32_t> luts;
     int n_boot = 0, max_rows = 0;
     // per executing context (keyed by the context): device tables + scratch
     std::mutex mu;   // compile + the state map; runs on distinct contexts proceed concurrently
@@ -223,6 +228,7 @@ int compile(TfheAmdCircuit *C) {
         } else {
             CircRow r;
             build_row(nd.c0, nd.s, A, 3, &r);
+            if (nd.gate == kLutGate) r.lut = nd.table + 1;   // table id + 1 until the layout is known (below)
             R.push_back(r);
             kss[L].push_back(CircKs{(int)R.size() - 1, -1, 0, w});
             C->n_boot += 1;
@@ -232,13 +238,23 @@ int compile(TfheAmdCircuit *C) {
     C->max_rows = 0;
     for (size_t L = 0; L < rows.size(); ++L) {
         TfheAmdCircuit::Level lv{(int)C->rows.size(), (int)rows[L].size(), (int)C->ks.size(), (int)kss[L].size(),
-                                 (int)C->lin.size(), (int)lins[L].size()};
+                                 (int)C->lin.size(), (int)lins[L].size(), false};
         if (lv.nrows > 65535) return TFHE_AMD_E_ARG;
+        for (const CircRow &r : rows[L]) lv.lut = lv.lut || r.lut != 0;
         C->rows.insert(C->rows.end(), rows[L].begin(), rows[L].end());
         C->ks.insert(C->ks.end(), kss[L].begin(), kss[L].end());
         C->lin.insert(C->lin.end(), lins[L].begin(), lins[L].end());
         C->levels.push_back(lv);
         C->max_rows = std::max(C->max_rows, lv.nrows);
+    }
+    // a LUT row's test vector: words from the row's own record to its table in the uploaded block
+    // [rows | ks | lin | tables] (tfhe_amd_circuit_run_dev_impl)
+    const size_t head = (sizeof(CircRow) * C->rows.size() + sizeof(CircKs) * C->ks.size() +
+                         sizeof(CircLin) * C->lin.size()) / 4;
+    if (head + C->luts.size() > 0x7fffffffu) return TFHE_AMD_E_ARG;
+    for (size_t i = 0; i < C->rows.size(); ++i) {
+        CircRow &r = C->rows[i];
+        if (r.lut) r.lut = (int32_t)(head + (size_t)(r.lut - 1) * kN - i * (sizeof(CircRow) / 4));
     }
     C->compiled = true;
     return TFHE_AMD_OK;
@@ -311,13 +327,43 @@ extern "C" int tfhe_amd_circuit_lincomb(TfheAmdCircuit *c, int32_t c0, int32_t s
     return add_node(c, n);
 }
 
+// Programmable-bootstrap nodes: a table is a copy of the caller's test vector; a LUT node is one
+// bootstrapped row whose accumulator starts from it
+extern "C" int tfhe_amd_circuit_lut_table(TfheAmdCircuit *c, const int32_t *tv) {
+    if (!c || !tv) return TFHE_AMD_E_ARG;
+    const int id = (int)(c->luts.size() / kN);
+    c->luts.insert(c->luts.end(), tv, tv + kN);
+    c->compiled = false;   // the uploaded block grows
+    return id;
+}
+
+extern "C" int tfhe_amd_circuit_lut_table_get(const TfheAmdCircuit *c, int table, int32_t *out) {
+    if (!c || !out || table < 0 || (size_t)table >= c->luts.size() / kN) return TFHE_AMD_E_ARG;
+    memcpy(out, c->luts.data() + (size_t)table * kN, sizeof(int32_t) * kN);
+    return TFHE_AMD_OK;
+}
+
+extern "C" int tfhe_amd_circuit_lut(TfheAmdCircuit *c, int table, int32_t c0, int32_t sa, int a, int32_t sb, int b,
+                                    int32_t sc, int cc) {
+    if (!c || a < 0 || table < 0 || (size_t)table >= c->luts.size() / kN) return TFHE_AMD_E_ARG;
+    Node n{1, kLutGate, c0, {sa, b >= 0 ? sb : 0, cc >= 0 ? sc : 0}, {a, b, cc}, table};
+    return add_node(c, n);
+}
+
+extern "C" int tfhe_amd_circuit_lut_node(const TfheAmdCircuit *c, int w, int *table, int32_t *c0) {
+    if (!c || w < 0 || w >= (int)c->nodes.size() || c->nodes[w].gate != kLutGate) return TFHE_AMD_E_ARG;
+    if (table) *table = c->nodes[w].table;
+    if (c0) *c0 = c->nodes[w].c0;
+    return TFHE_AMD_OK;
+}
+
 extern "C" int tfhe_amd_circuit_node(const TfheAmdCircuit *c, int w, int *kind, int *gate, int32_t *c0, int32_t *s,
                                      int *in) {
     if (!c || w < 0 || w >= (int)c->nodes.size()) return TFHE_AMD_E_ARG;
     const Node &n = c->nodes[w];
     if (kind) *kind = n.kind;
     if (gate) *gate = n.gate;
-    if (c0) *c0 = n.c0;
+    if (c0) *c0 = n.gate == kLutGate ? n.table : n.c0;   // a LUT node: the table id (tfhe_amd_circuit_lut_node)
     for (int t = 0; t < 3; ++t) {
         if (s) s[t] = n.s[t];
         if (in) in[t] = n.in[t];
@@ -375,7 +421,7 @@ int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int de
         st->release();
         st->dev = device;
         const size_t bytes = sizeof(CircRow) * c->rows.size() + sizeof(CircKs) * c->ks.size() +
-                             sizeof(CircLin) * c->lin.size() + 64;
+                             sizeof(CircLin) * c->lin.size() + sizeof(int32_t) * c->luts.size() + 64;
         if (hipMalloc(&st->d_tab, bytes) != hipSuccess) return TFHE_AMD_E_NOMEM;
         char *p = (char *)st->d_tab;
         if (!c->rows.empty() && hipMemcpy(p, c->rows.data(), sizeof(CircRow) * c->rows.size(),
@@ -386,6 +432,9 @@ int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int de
         p += sizeof(CircKs) * c->ks.size();
         if (!c->lin.empty() && hipMemcpy(p, c->lin.data(), sizeof(CircLin) * c->lin.size(),
                                          hipMemcpyHostToDevice) != hipSuccess) return TFHE_AMD_E_HIP;
+        p += sizeof(CircLin) * c->lin.size();   // the LUT rows' self-relative offsets (compile) point here
+        if (!c->luts.empty() && hipMemcpy(p, c->luts.data(), sizeof(int32_t) * c->luts.size(),
+                                          hipMemcpyHostToDevice) != hipSuccess) return TFHE_AMD_E_HIP;
     }
     const size_t need = (size_t)c->max_rows * B;
     if (need > st->u_slots) {
@@ -405,7 +454,8 @@ int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int de
     const CircLin *d_lin = (const CircLin *)(d_ks + c->ks.size());
     for (const auto &lv : c->levels) {
         if (lv.nrows) {
-            const Guard gd = guard_stats ? Guard{st->u_flags, guard_stats} : Guard{};
+            Guard gd = guard_stats ? Guard{st->u_flags, guard_stats} : Guard{};
+            gd.lut_rows = lv.lut;   // the launch takes the rows kernels' LUT instantiation
             const hipError_t e =
                 launch_blind_rotate_rows(key, B, lv.nrows, d_rows + lv.row0, wa, wb, kE8, st->u_a, st->u_b, s, &gd);
             if (e != hipSuccess) return TFHE_AMD_E_HIP;

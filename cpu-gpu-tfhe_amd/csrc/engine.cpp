@@ -133,7 +133,11 @@ hipError_t launch_blind_rotate_rows(const DeviceKey &key, int B, int nrows, cons
                                     const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
                                     const Guard *guard) {
     switch (br_version()) {
-    case 4: return launch_blind_rotate_v4_rows(key, B, nrows, rows, wa, wb, mu, u_a, u_b, s);
+    case 4: {
+        const Guard lut_only{nullptr, nullptr, true};   // no flags: not guard mode, LUT rows present
+        return launch_blind_rotate_v4_rows(key, B, nrows, rows, wa, wb, mu, u_a, u_b, s,
+                                           guard && guard->lut_rows ? &lut_only : nullptr);
+    }
     default: {
         hipError_t e = launch_blind_rotate_v6_rows(key, B, nrows, rows, wa, wb, mu, u_a, u_b, s, guard);
         if (e != hipSuccess || !guard || !guard->flags) return e;
@@ -691,6 +695,59 @@ extern "C" int tfhe_amd_bootstrap_batch_dev(TfheAmdContext *c, int B, int32_t mu
     HIPCHK(launch_keyswitch(c->key, B, c->u_a, c->u_b, nullptr, nullptr, 0, res_a, res_b, s));
     HIPCHK(c->fence.done(s));
     return TFHE_AMD_OK;
+}
+
+// ------------------------------------------------------------------ programmable bootstrapping
+
+extern "C" int tfhe_amd_lut_fill(int32_t *tv, int p, const int32_t *values) {
+    if (!tv || !values || p < 1 || p > kN || (p & (p - 1))) return TFHE_AMD_E_ARG;
+    for (int j = 0; j < kN; ++j) tv[j] = values[(int)(((long)j * p) >> kLogN)];   // floor(j p / N)
+    return TFHE_AMD_OK;
+}
+
+// B bootstraps of (0, c) + sa X + sb Y through the tables tv [n_lut][kN] (engine.h BrInput); ks:
+// followed by the key switch into out (n = 500), else out is the extracted sample (N = 1024)
+static int lut_batch_dev(TfheAmdContext *c, bool ks, int B, int n_lut, const int32_t *tv, const int32_t *lut_index,
+                         int32_t cst, int32_t sa, const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                         const int32_t *y_a, const int32_t *y_b, int32_t *out_a, int32_t *out_b, void *stream) {
+    if (!c || B < 0 || n_lut <= 0 || !tv || !c->key.has_bk || (ks && !c->key.ksk)) return TFHE_AMD_E_ARG;
+    if (B == 0) return TFHE_AMD_OK;
+    if (!x_a || !x_b || !out_a || !out_b || (sb && (!y_a || !y_b))) return TFHE_AMD_E_ARG;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceScope dev_scope(c->device);
+    HIPCHK(dev_scope.rc);
+    TraceScope trace(c);
+    int rc = tfhe_amd_reserve(c, B);   // guard flags (and the extracted samples) live in the context's scratch
+    if (rc) return rc;
+    HIPCHK(c->fence.acquire(s));
+    BrInput in{x_a, x_b, sb ? y_a : nullptr, sb ? y_b : nullptr, cst, sa, sb, n_lut, tv, lut_index};
+    {
+        ProfScope ps(c, s, true);
+        const Guard gd = ctx_guard(c);
+        HIPCHK(run_br(c->key, B, 1, &in, 0, ks ? c->u_a : out_a, ks ? c->u_b : out_b, s, &gd));
+    }
+    if (ks) {
+        ProfScope ps(c, s, false);
+        HIPCHK(launch_keyswitch(c->key, B, c->u_a, c->u_b, nullptr, nullptr, 0, out_a, out_b, s));
+    }
+    HIPCHK(c->fence.done(s));
+    return TFHE_AMD_OK;
+}
+
+extern "C" int tfhe_amd_bootstrap_lut_woks_batch_dev(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,
+                                                     const int32_t *lut_index, int32_t cst, int32_t sa,
+                                                     const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                                     const int32_t *y_a, const int32_t *y_b, int32_t *u_a,
+                                                     int32_t *u_b, void *stream) {
+    return lut_batch_dev(c, false, B, n_lut, tv, lut_index, cst, sa, x_a, x_b, sb, y_a, y_b, u_a, u_b, stream);
+}
+extern "C" int tfhe_amd_bootstrap_lut_batch_dev(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,
+                                                const int32_t *lut_index, int32_t cst, int32_t sa,
+                                                const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                                const int32_t *y_a, const int32_t *y_b, int32_t *res_a,
+                                                int32_t *res_b, void *stream) {
+    return lut_batch_dev(c, true, B, n_lut, tv, lut_index, cst, sa, x_a, x_b, sb, y_a, y_b, res_a, res_b, stream);
 }
 
 extern "C" int tfhe_amd_keyswitch_batch_dev(TfheAmdContext *c, int B, const int32_t *u_a, const int32_t *u_b,
@@ -1462,6 +1519,65 @@ extern "C" int tfhe_amd_bootstrap_batch_host(TfheAmdContext *c, int B, int32_t m
 extern "C" int tfhe_amd_keyswitch_batch_host(TfheAmdContext *c, int B, const int32_t *u_a, const int32_t *u_b,
                                              int32_t *res_a, int32_t *res_b) {
     return single_input_host(c, OP_KS, B, 0, u_a, u_b, res_a, res_b);
+}
+
+// programmable bootstrap, host arrays: the staged path of single_input_host with the tables
+// (n_lut x 4 KB) and the table indices uploaded beside the inputs (in-place safe)
+static int lut_batch_host(TfheAmdContext *c, bool ks, int B, int n_lut, const int32_t *tv, const int32_t *lut_index,
+                          int32_t cst, int32_t sa, const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                          const int32_t *y_a, const int32_t *y_b, int32_t *out_a, int32_t *out_b) {
+    if (!c || B < 0 || n_lut <= 0 || !tv) return TFHE_AMD_E_ARG;
+    if (lut_index)
+        for (int i = 0; i < B; ++i)
+            if (lut_index[i] < 0 || lut_index[i] >= n_lut) return TFHE_AMD_E_ARG;
+    if (B == 0) return TFHE_AMD_OK;
+    if (!x_a || !x_b || !out_a || !out_b || (sb && (!y_a || !y_b))) return TFHE_AMD_E_ARG;
+    // [x_a | x_b | y_a | y_b | tables | indices | out_a | out_b] in the io scratch (4 cap x 501 words)
+    const int dout = ks ? kn : kN;
+    const size_t Ai = (size_t)B * kn, Ao = (size_t)B * dout, Tw = (size_t)n_lut * kN;
+    const size_t o_y = Ai + B, o_tv = o_y + (sb ? Ai + B : 0), o_ix = o_tv + Tw, o_out = o_ix + (lut_index ? B : 0);
+    const size_t need = o_out + Ao + B, cap = (need + io_words(1) - 1) / io_words(1);
+    if (cap > ((size_t)1 << 24)) return TFHE_AMD_E_ARG;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceScope dev_scope(c->device);
+    HIPCHK(dev_scope.rc);
+    TraceScope trace(c);
+    int rc = tfhe_amd_reserve(c, std::max(B, (int)cap));
+    if (rc) return rc;
+    int32_t *h = c->h_io, *d = c->io;
+    memcpy(h, x_a, Ai * 4);
+    memcpy(h + Ai, x_b, (size_t)B * 4);
+    if (sb) {
+        memcpy(h + o_y, y_a, Ai * 4);
+        memcpy(h + o_y + Ai, y_b, (size_t)B * 4);
+    }
+    memcpy(h + o_tv, tv, Tw * 4);
+    if (lut_index) memcpy(h + o_ix, lut_index, (size_t)B * 4);
+    HIPCHK(hipMemcpyAsync(d, h, o_out * 4, hipMemcpyHostToDevice, c->stream));
+    int32_t *oa = d + o_out, *ob = oa + Ao;
+    rc = lut_batch_dev(c, ks, B, n_lut, d + o_tv, lut_index ? d + o_ix : nullptr, cst, sa, d, d + Ai, sb,
+                       sb ? d + o_y : nullptr, sb ? d + o_y + Ai : nullptr, oa, ob, c->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(h + o_out, oa, (Ao + B) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(out_a, h + o_out, Ao * 4);
+    memcpy(out_b, h + o_out + Ao, (size_t)B * 4);
+    return TFHE_AMD_OK;
+}
+
+extern "C" int tfhe_amd_bootstrap_lut_woks_batch_host(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,
+                                                      const int32_t *lut_index, int32_t cst, int32_t sa,
+                                                      const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                                      const int32_t *y_a, const int32_t *y_b, int32_t *u_a,
+                                                      int32_t *u_b) {
+    return lut_batch_host(c, false, B, n_lut, tv, lut_index, cst, sa, x_a, x_b, sb, y_a, y_b, u_a, u_b);
+}
+extern "C" int tfhe_amd_bootstrap_lut_batch_host(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,
+                                                 const int32_t *lut_index, int32_t cst, int32_t sa,
+                                                 const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                                 const int32_t *y_a, const int32_t *y_b, int32_t *res_a,
+                                                 int32_t *res_b) {
+    return lut_batch_host(c, true, B, n_lut, tv, lut_index, cst, sa, x_a, x_b, sb, y_a, y_b, res_a, res_b);
 }
 
 // largest batch the host path runs unsliced, i.e. whose key-switch inputs are all in the scratch

@@ -30,17 +30,29 @@ constexpr int kTw4Words = 2 * 16 + 2 * 27 * 64 + 2 * 16 * 64;
 constexpr int kTw6Words = 4 + 4 * 4 * 64 + 8 * 64 + 2 * 64;   // fft_wave.h table map
 
 // x = (0, c) + sa * X + sb * Y   (gate prologue, boot-gates.cu:98-397; Y unused if sb == 0)
+// Programmable bootstrap: with tv set the accumulator starts from the caller's
+// test vector, ACC = (0, X^{2N - barb} tv[t]), instead of the constant (mu, ..., mu), and the
+// launchers pick the kernels' LUT instantiation.  tv = [n_lut][kN] on the device; ciphertext g
+// takes table t = lut_index[g] (null: table 0), clamped by the kernel into [0, n_lut) before any
+// address is formed.  The launchers' mu is unused then.
 struct BrInput {
     const int32_t *x_a, *x_b;
     const int32_t *y_a, *y_b;
     int32_t c, sa, sb;
+    int32_t n_lut = 0;
+    const int32_t *tv = nullptr;
+    const int32_t *lut_index = nullptr;
 };
 
 // One bootstrapped row of a circuit level (circuit.cpp): the blind rotation input is
 // (0, c) + sa W[x] + sb W[y] + sc W[z] over wire indices (-1 = absent; x is always present).
+// lut: 0 = the constant test vector (mu, ..., mu); otherwise the row's test vector of kN words
+// starts `lut` 32-bit words after the row's own record, in the same device allocation (the level
+// tables and the circuit's LUT tables are uploaded as one block, so the offset is the same on every
+// device).  Only launches whose Guard says lut_rows read it.
 struct CircRow {
     int32_t c, sa, sb, sc;
-    int32_t x, y, z, pad;
+    int32_t x, y, z, lut;
 };
 // One key-switched circuit output: W[out] = KS(u[r1] (+ u[r2] if r2 >= 0) + (0, add_b)).
 struct CircKs {
@@ -101,9 +113,13 @@ struct StreamFence {
 // an exact-NTT (v4) launch in guard mode then recomputes every ciphertext whose flag reaches the
 // threshold (1/8 by default) and exits at once for all others.  stats[0] counts the recomputed
 // ciphertexts, stats[1] holds the largest high word seen (tfhe_amd_guard_stats).
+// lut_rows (rows launches only): some row of the level carries a test vector (CircRow.lut), so
+// the rows launchers take the kernels' LUT instantiation; it rides here because the row records
+// themselves are in device memory.  With flags null it is the only thing the struct says.
 struct Guard {
     uint32_t *flags = nullptr;
     uint32_t *stats = nullptr;
+    bool lut_rows = false;
 };
 uint32_t guard_threshold_hi();
 
@@ -147,7 +163,8 @@ int br_version();
 // smoke or bench run can say which kernels produced the results it checked.
 void trace_kernel(const char *name);
 // circuit level blind rotation with the selected kernel (rows variants of v4 / v5 / v6); the
-// default fp64 kernel runs guarded (flags: 2 words per row x instance)
+// default fp64 kernel runs guarded (flags: 2 words per row x instance); guard->lut_rows picks the
+// LUT instantiations (in exact mode too, where the flags are not used)
 hipError_t launch_blind_rotate_rows(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                     const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
                                     const Guard *guard);

@@ -59,4 +59,21 @@ __device__ __forceinline__ int modswitch_2N(uint32_t x) {
     return (int)((((uint64_t)x + (1u << 20)) >> 21) & (k2N - 1));
 }
 
+// Programmable bootstrap (engine.h BrInput), both kernel generations.
+// The test vector of ciphertext idx out of tv [n_lut][kN]: the index comes from device memory
+// unchecked by the host, so it is clamped into [0, n_lut) before it forms an address.
+__device__ __forceinline__ const int32_t *lut_table(const int32_t *tv, const int32_t *lut_index, int n_lut, int idx) {
+    int t = lut_index ? lut_index[idx] : 0;
+    t = t < n_lut ? t : n_lut - 1;
+    t = t > 0 ? t : 0;
+    return tv + (size_t)t * kN;
+}
+// Coefficient k (of the 2N-periodic negacyclic extension) of X^e tv: tv[(k - e) mod N], negated
+// when (k - e) mod 2N >= N.  With tv = (mu, ..., mu) this is the constant path's expression.
+__device__ __forceinline__ uint32_t lut_coeff(const int32_t *tv, int k, int e) {
+    const int d = (k - e) & (k2N - 1);
+    const uint32_t v = (uint32_t)tv[d & (kN - 1)];
+    return (d & kN) ? 0u - v : v;
+}
+
 }  // namespace tfhe_amd

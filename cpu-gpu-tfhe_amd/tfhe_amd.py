@@ -73,6 +73,13 @@ def _load():
     L.tfhe_amd_bootstrap_woks_batch_host.argtypes = [_VP, ctypes.c_int, ctypes.c_int32] + [_I32P] * 4
     L.tfhe_amd_bootstrap_batch_host.argtypes = [_VP, ctypes.c_int, ctypes.c_int32] + [_I32P] * 4
     L.tfhe_amd_keyswitch_batch_host.argtypes = [_VP, ctypes.c_int] + [_I32P] * 4
+    L.tfhe_amd_lut_fill.argtypes = [_I32P, ctypes.c_int, _I32P]
+    for f in ("tfhe_amd_bootstrap_lut_woks_batch_dev", "tfhe_amd_bootstrap_lut_batch_dev"):
+        getattr(L, f).argtypes = ([_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, ctypes.c_int32, ctypes.c_int32, _VP, _VP,
+                                   ctypes.c_int32] + [_VP] * 4 + [_VP])
+    for f in ("tfhe_amd_bootstrap_lut_woks_batch_host", "tfhe_amd_bootstrap_lut_batch_host"):
+        getattr(L, f).argtypes = ([_VP, ctypes.c_int, ctypes.c_int, _I32P, _I32P, ctypes.c_int32, ctypes.c_int32, _I32P,
+                                   _I32P, ctypes.c_int32] + [_I32P] * 4)
     L.tfhe_amd_blind_rotate_dev.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]
     L.tfhe_amd_external_product_dev.argtypes = [_VP, ctypes.c_int, _VP, _VP, _VP]
     L.tfhe_amd_context_create_replica.argtypes = [_VP, ctypes.c_int, ctypes.POINTER(_VP)]
@@ -177,6 +184,44 @@ def i32(x):
     if a.dtype == np.int32 and a.flags["C_CONTIGUOUS"]:
         return a
     return np.ascontiguousarray(a.astype(np.int64).astype(np.int32))
+
+
+# ---- programmable bootstrapping: the encoding convention of include/tfhe_amd.h (tfhe_amd_lut_fill)
+
+def _lut_p(p):
+    p = int(p)
+    if p < 1 or p > N or p & (p - 1):
+        raise TfheAmdError(f"p must be a power of two in [1, {N}], got {p}")
+    return p
+
+
+def lut_encode(m, p):
+    """Torus32 of message m in [0, p): (2m + 1) / (4p), the centre of box m of the half torus."""
+    p = _lut_p(p)
+    m = np.asarray(m, dtype=np.int64)
+    if np.any((m < 0) | (m >= p)):
+        raise TfheAmdError(f"message outside [0, {p})")
+    return ((2 * m + 1) * ((1 << 30) // p)).astype(np.int32)
+
+
+def lut_decode(phase, p):
+    """The box of the half torus a phase (Torus32) lies in: floor(2p phase), the message when it is
+    in [0, p); values in [p, 2p) mean the phase left the half torus [0, 1/2)."""
+    p = _lut_p(p)
+    ph = np.asarray(phase).astype(np.int64) & 0xFFFFFFFF
+    return (ph * p) >> 31
+
+
+def lut_table(p, values):
+    """tfhe_amd_lut_fill: the test vector int32 [1024] with tv[j] = values[floor(j p / N)], so an
+    input encoding m (lut_encode(m, p)) bootstraps to values[m] (Torus32 words, e.g.
+    lut_encode(f(m), p2))."""
+    v = np.ascontiguousarray(np.asarray(values).astype(np.int64).astype(np.int32))
+    if v.ndim != 1 or v.shape[0] != int(p):
+        raise TfheAmdError(f"values: need {p} Torus32 words, got shape {v.shape}")
+    tv = np.zeros(N, np.int32)
+    _check(lib.tfhe_amd_lut_fill(_p(tv), int(p), _p(v)), "lut_fill")
+    return tv
 
 
 class _PinnedBlock:
@@ -339,6 +384,16 @@ class SecretKeyset:
         B = bits.shape[0]
         a = rng.integers(-2**31, 2**31, (B, n_lwe), dtype=np.int64)
         mu = np.where(bits != 0, MU, -MU)
+        noise = np.rint(rng.normal(0.0, stdev, B) * 2**32).astype(np.int64)
+        b = (a @ self.lwe_key.astype(np.int64) + mu + noise)
+        return i32(a), i32(b)
+
+    def encrypt_digits(self, m, p, rng, stdev=2.4349504419032758e-05):
+        """fresh encryptions of messages m in [0, p) at the programmable bootstrap's encoding
+        (lut_encode: (2m + 1) / (4p))."""
+        mu = lut_encode(m, p).astype(np.int64)
+        B = mu.shape[0]
+        a = rng.integers(-2**31, 2**31, (B, n_lwe), dtype=np.int64)
         noise = np.rint(rng.normal(0.0, stdev, B) * 2**32).astype(np.int64)
         b = (a @ self.lwe_key.astype(np.int64) + mu + noise)
         return i32(a), i32(b)
@@ -525,6 +580,61 @@ class Context:
         _check(lib.tfhe_amd_gate_batch_dev(self.h, g, B, ptr(res_a), ptr(res_b), ptr(ca_a), ptr(ca_b),
                                            ptr(cb_a), ptr(cb_b), ptr(cc_a), ptr(cc_b), stream),
                "gate_batch_dev")
+
+    # ---- programmable bootstrapping (tfhe_amd_bootstrap_lut_*): tv = test vectors [n_lut][1024] (or
+    # one [1024]), lut_index [B] picks each ciphertext's table (None: table 0); the blind-rotation
+    # input is (0, c) + sa X + sb Y
+    def _lut_host(self, ks, tv, x_a, x_b, lut_index, c, sa, sb, y_a, y_b):
+        tv = i32(tv).reshape(-1, N)
+        x_a = i32(x_a); B = x_a.shape[0]
+        idx = None if lut_index is None else i32(lut_index)
+        if idx is not None and idx.shape != (B,):
+            raise TfheAmdError(f"lut_index: need one table index per ciphertext ({B}), got {idx.shape}")
+        if int(sb) != 0 and (y_a is None or y_b is None):
+            raise TfheAmdError("sb != 0 needs y_a, y_b")
+        r_a = np.zeros((B, n_lwe if ks else N), np.int32); r_b = np.zeros(B, np.int32)
+        fn = lib.tfhe_amd_bootstrap_lut_batch_host if ks else lib.tfhe_amd_bootstrap_lut_woks_batch_host
+        _check(fn(self.h, B, tv.shape[0], _p(tv), _p(idx), int(c), int(sa), _p(x_a), _p(i32(x_b)), int(sb),
+                  _p(None if y_a is None else i32(y_a)), _p(None if y_b is None else i32(y_b)), _p(r_a), _p(r_b)),
+               "bootstrap_lut_batch_host" if ks else "bootstrap_lut_woks_batch_host")
+        return r_a, r_b
+
+    def lut_woks_host(self, tv, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None):
+        """tfhe_amd_bootstrap_lut_woks_batch_host -> the extracted samples (u_a [B][1024], u_b [B])"""
+        return self._lut_host(False, tv, x_a, x_b, lut_index, c, sa, sb, y_a, y_b)
+
+    def lut_bootstrap_host(self, tv, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None):
+        """tfhe_amd_bootstrap_lut_batch_host -> the key-switched results (r_a [B][500], r_b [B])"""
+        return self._lut_host(True, tv, x_a, x_b, lut_index, c, sa, sb, y_a, y_b)
+
+    def _lut_dev(self, ks, tv, out_a, out_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream):
+        B = x_a.shape[0]
+        if tv is None or tv.dim() != 2 or tv.shape[0] < 1:
+            raise TfheAmdError("tv: need a GPU tensor [n_lut][1024]")
+        n_lut = tv.shape[0]
+        named = [("tv", tv, (n_lut, N)), ("out_a", out_a, (B, n_lwe if ks else N)), ("out_b", out_b, (B,)),
+                 ("x_a", x_a, (B, n_lwe)), ("x_b", x_b, (B,))]
+        if lut_index is not None:
+            named.append(("lut_index", lut_index, (B,)))
+        if int(sb) != 0:
+            named += [("y_a", y_a, (B, n_lwe)), ("y_b", y_b, (B,))]
+        for name, t, shape in named:
+            self._dev_check(t, shape, name)
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        fn = lib.tfhe_amd_bootstrap_lut_batch_dev if ks else lib.tfhe_amd_bootstrap_lut_woks_batch_dev
+        _check(fn(self.h, B, n_lut, ptr(tv), ptr(lut_index), int(c), int(sa), ptr(x_a), ptr(x_b), int(sb),
+                  ptr(y_a) if int(sb) else None, ptr(y_b) if int(sb) else None, ptr(out_a), ptr(out_b), stream),
+               "bootstrap_lut_batch_dev" if ks else "bootstrap_lut_woks_batch_dev")
+
+    def lut_woks_dev(self, tv, u_a, u_b, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None, stream=None):
+        """tfhe_amd_bootstrap_lut_woks_batch_dev on torch tensors (as gate_dev); a lut_index entry
+        outside [0, n_lut) is clamped by the kernel"""
+        self._lut_dev(False, tv, u_a, u_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream)
+
+    def lut_bootstrap_dev(self, tv, res_a, res_b, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None,
+                          stream=None):
+        """tfhe_amd_bootstrap_lut_batch_dev on torch tensors; res may alias x"""
+        self._lut_dev(True, tv, res_a, res_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream)
 
     def blind_rotate_dev(self, acc, bara, iters, stream=None):
         B = acc.shape[0]
@@ -715,6 +825,12 @@ lib.tfhe_amd_circuit_inputs.argtypes = [_VP, ctypes.c_int]
 lib.tfhe_amd_circuit_gate.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
 lib.tfhe_amd_circuit_lincomb.argtypes = [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_int32,
                                          ctypes.c_int, ctypes.c_int32, ctypes.c_int]
+LUT_GATE = -2   # gate code tfhe_amd_circuit_node reports for a programmable-bootstrap node
+lib.tfhe_amd_circuit_lut_table.argtypes = [_VP, _I32P]
+lib.tfhe_amd_circuit_lut_table_get.argtypes = [_VP, ctypes.c_int, _I32P]
+lib.tfhe_amd_circuit_lut.argtypes = [_VP, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_int32,
+                                     ctypes.c_int, ctypes.c_int32, ctypes.c_int]
+lib.tfhe_amd_circuit_lut_node.argtypes = [_VP, ctypes.c_int, _IP, ctypes.POINTER(ctypes.c_int32)]
 lib.tfhe_amd_circuit_info.argtypes = [_VP, _IP, _IP, _IP, _IP]
 lib.tfhe_amd_circuit_level_sizes.argtypes = [_VP, _IP, ctypes.c_int]
 lib.tfhe_amd_circuit_node.argtypes = [_VP, ctypes.c_int, _IP, _IP, ctypes.POINTER(ctypes.c_int32),
@@ -783,6 +899,31 @@ class Circuit:
     def lincomb(self, c0, sa, a, sb=0, b=-1, sc=0, c=-1):
         return self._w(lib.tfhe_amd_circuit_lincomb(self.h, int(c0), int(sa), int(a), int(sb), int(b), int(sc),
                                                     int(c)), "lincomb")
+
+    def lut_table(self, tv):
+        """tfhe_amd_circuit_lut_table: register a test vector int32 [1024] (lut_table(p, values));
+        returns its table id"""
+        tv = i32(tv)
+        if tv.shape != (N,):
+            raise TfheAmdError(f"tv: need {N} Torus32 words, got shape {tv.shape}")
+        return self._w(lib.tfhe_amd_circuit_lut_table(self.h, _p(tv)), "lut_table")
+
+    def lut_table_get(self, table):
+        out = np.zeros(N, np.int32)
+        _check(lib.tfhe_amd_circuit_lut_table_get(self.h, int(table), _p(out)), "lut_table_get")
+        return out
+
+    def lut(self, table, c0, sa, a, sb=0, b=-1, sc=0, c=-1):
+        """tfhe_amd_circuit_lut: one programmable bootstrap of (0, c0) + sa*a + sb*b + sc*c through
+        `table`; returns the new wire"""
+        return self._w(lib.tfhe_amd_circuit_lut(self.h, int(table), int(c0), int(sa), int(a), int(sb), int(b),
+                                                int(sc), int(c)), "lut")
+
+    def lut_node(self, w):
+        """(table id, c0) of the LUT node w (node(w) reports gate -2 and the table id as c0)"""
+        t, c0 = ctypes.c_int(), ctypes.c_int32()
+        _check(lib.tfhe_amd_circuit_lut_node(self.h, int(w), ctypes.byref(t), ctypes.byref(c0)), "circuit_lut_node")
+        return t.value, c0.value
 
     def _vec(self, fn, a, b, n_out, *extra):
         out = (ctypes.c_int * n_out)()
@@ -880,6 +1021,9 @@ class Circuit:
             return np.where(x > 0, e8, -e8).astype(np.int64)
         for w in range(n_w):
             kind, gate, c0, s, ins = self.node(w)
+            if gate == LUT_GATE:
+                raise TfheAmdError(f"eval_plain evaluates bits; wire {w} is a LUT node (multi-valued): evaluate it "
+                                   "from its table (lut_node, lut_table_get)")
             if kind == 0:
                 val[w] = np.where(np.asarray(bits[w]) != 0, e8, -e8).astype(np.int64)
             elif kind == 2:

@@ -142,6 +142,54 @@ int tfhe_amd_keyswitch_batch_host(TfheAmdContext *ctx, int B,
                                   const int32_t *u_a, const int32_t *u_b,
                                   int32_t *res_a, int32_t *res_b);
 
+/* ---- Programmable bootstrapping: a bootstrap that evaluates a caller-supplied
+ * function.  The blind rotation starts from ACC = (0, X^{2N - barb} tv) with a test vector tv of
+ * N = 1024 Torus32 coefficients instead of the constant (mu, ..., mu) of the sign bootstrap
+ * above, so the extracted sample encrypts tv[round(2N phase)] for a phase in [0, 1/2) and
+ * -tv[round(2N phase) - N] in [1/2, 1) (the rotation is negacyclic).
+ *
+ * Encoding convention (tfhe_amd_lut_fill and the Python helpers): a message m in [0, p) sits at
+ * the torus value (2m + 1) / (4p), the centre of box m of the p boxes of the half torus [0, 1/2),
+ * and tv[j] = values[floor(j p / N)], so box m reads values[m]: a fresh output when the input's
+ * phase error stays below 1/(4p).  Table values meant to be looked up again are encoded the same
+ * way, values[m] = (2 f(m) + 1) / (4p') as a Torus32.  p must be a power of two in [1, 1024];
+ * anything else, or a null pointer, returns TFHE_AMD_E_ARG.  Host only, needs no GPU. */
+int tfhe_amd_lut_fill(int32_t tv[1024], int p, const int32_t *values /* [p] */);
+
+/* B programmable bootstraps in one launch.  The blind-rotation input is (0, c) + sa*X + sb*Y (the
+ * gate prologue's form; Y is ignored and may be NULL when sb == 0).  tv = n_lut tables of 1024
+ * words; ciphertext i takes table lut_index[i] (NULL: table 0).  u = SampleExtract_0 of the rotated
+ * accumulator: u_a [B][1024], u_b [B]; the non-woks forms key switch it into res_a [B][500],
+ * res_b [B], which may alias X.  All arrays of the _dev forms are on the context's device and the
+ * call is asynchronous on `stream` (0: the context's); there the kernel clamps each lut_index entry
+ * into [0, n_lut) before it forms an address, so a bad device-side index reads another table but
+ * never out of bounds.  The _host forms take host arrays, upload the tables (n_lut x 4 KB) with the
+ * inputs, run synchronously and return TFHE_AMD_E_ARG for a lut_index entry outside [0, n_lut).
+ * TFHE_AMD_E_ARG also for n_lut <= 0, a null tv and B < 0.  The exactness guard (the flagged
+ * ciphertexts are recomputed with the same table), tfhe_amd_select_kernel and
+ * tfhe_amd_set_guard_threshold apply as to every other bootstrap; tfhe_amd_last_kernels names the
+ * LUT variants, e.g. "k_blind_rotate_v6(lut+reg-rotation)", "k_blind_rotate_v4(lut+guard)". */
+int tfhe_amd_bootstrap_lut_woks_batch_dev(TfheAmdContext *ctx, int B, int n_lut, const int32_t *tv,
+                                          const int32_t *lut_index, int32_t c, int32_t sa,
+                                          const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                          const int32_t *y_a, const int32_t *y_b,
+                                          int32_t *u_a, int32_t *u_b, void *stream);
+int tfhe_amd_bootstrap_lut_batch_dev(TfheAmdContext *ctx, int B, int n_lut, const int32_t *tv,
+                                     const int32_t *lut_index, int32_t c, int32_t sa,
+                                     const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                     const int32_t *y_a, const int32_t *y_b,
+                                     int32_t *res_a, int32_t *res_b, void *stream);
+int tfhe_amd_bootstrap_lut_woks_batch_host(TfheAmdContext *ctx, int B, int n_lut, const int32_t *tv,
+                                           const int32_t *lut_index, int32_t c, int32_t sa,
+                                           const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                           const int32_t *y_a, const int32_t *y_b,
+                                           int32_t *u_a, int32_t *u_b);
+int tfhe_amd_bootstrap_lut_batch_host(TfheAmdContext *ctx, int B, int n_lut, const int32_t *tv,
+                                      const int32_t *lut_index, int32_t c, int32_t sa,
+                                      const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                      const int32_t *y_a, const int32_t *y_b,
+                                      int32_t *res_a, int32_t *res_b);
+
 /* Debug/parity entry: run `iters` CMux steps of the blind rotation (i = 0..iters-1,
  * tfhe_MuxRotate_FFT, skipping bara_i == 0 like tfhe_blindRotate_FFT) on B explicit
  * accumulators acc [B][2][1024] in place, with rotations bara [B][iters].  The raw steps of the
@@ -327,9 +375,27 @@ int tfhe_amd_circuit_gate(TfheAmdCircuit *c, int gate, int a, int b, int cc);
  * (b, cc may be -1); the building block of threshold gates */
 int tfhe_amd_circuit_lincomb(TfheAmdCircuit *c, int32_t c0, int32_t sa, int a, int32_t sb, int b, int32_t sc,
                              int cc);
+/* Programmable-bootstrap nodes (the batch form and the encoding convention: above, at
+ * tfhe_amd_lut_fill).  tfhe_amd_circuit_lut_table registers a copy of a test vector with the
+ * circuit and returns its table id (>= 0); tfhe_amd_circuit_lut_table_get reads one back.
+ * tfhe_amd_circuit_lut adds one bootstrapped row, levelled like any other:
+ * wire = KS(SampleExtract_0(BlindRotate((0, X^{2N - barb} tv[table])))) for the input
+ * (0, c0) + sa*a + sb*b + sc*cc (b, cc may be -1).  It may share a level, and so one launch, with
+ * gate rows and with rows of other tables; the tables travel to each device with the level
+ * tables.  The output is whatever the table holds, so bit gates and the integer builders below
+ * may only read it if the table's values are +-1/8.  TFHE_AMD_E_ARG for an unknown table or
+ * wire. */
+int tfhe_amd_circuit_lut_table(TfheAmdCircuit *c, const int32_t tv[1024]);
+int tfhe_amd_circuit_lut(TfheAmdCircuit *c, int table, int32_t c0, int32_t sa, int a, int32_t sb, int b,
+                         int32_t sc, int cc);
+int tfhe_amd_circuit_lut_table_get(const TfheAmdCircuit *c, int table, int32_t out[1024]);
 /* node w as built: kind 0 input / 1 bootstrapped / 2 linear, gate code (-1 = lincomb),
- * constant, coefficients[3], inputs[3] (for host-side plaintext evaluation in tests) */
+ * constant, coefficients[3], inputs[3] (for host-side plaintext evaluation in tests).
+ * A LUT node reports kind 1, gate code -2 and its TABLE ID in *c0 (coefficients and inputs as a
+ * lincomb); its constant c0 is read with tfhe_amd_circuit_lut_node, which returns
+ * TFHE_AMD_E_ARG for any other node.  The fields of all other node kinds are as before. */
 int tfhe_amd_circuit_node(const TfheAmdCircuit *c, int w, int *kind, int *gate, int32_t *c0, int32_t *s, int *in);
+int tfhe_amd_circuit_lut_node(const TfheAmdCircuit *c, int w, int *table, int32_t *c0);
 /* compile (if needed) and report size: wires, gates, bootstraps per instance, depth */
 int tfhe_amd_circuit_info(TfheAmdCircuit *c, int *n_wires, int *n_gates, int *n_bootstraps, int *depth);
 /* rows (bootstraps) per level, level 0 first (level 0 is bootstrap-free); returns #levels */
