@@ -158,10 +158,13 @@ struct RowTerms {
 // prologue + modswitch + 500 CMux steps + extraction of one ciphertext into (ua, *ub).
 // LUT (programmable bootstrap, compile-time): the accumulator starts from the test vector tv [kN]
 // in device memory; tv = null (a constant row beside LUT rows) keeps the constant (mu, ..., mu)
-template <bool LUT = false>
+// MANY (many-LUT bootstrap; implies LUT): the modulus switch to a multiple of
+// 2^mo.th and the extraction of the coefficients 0 .. mo.n_out - 1 (modarith.h ManyOut)
+template <bool LUT = false, bool MANY = false>
 __device__ __forceinline__ void br_v4_body(V4Shared &sh, const V4Args &g, const RowTerms &t, int32_t mu,
                                            int32_t *__restrict__ ua, int32_t *__restrict__ ub,
-                                           const int32_t *__restrict__ tv = nullptr) {
+                                           const int32_t *__restrict__ tv = nullptr,
+                                           const ManyOut &mo = ManyOut{}) {
     const int tid = threadIdx.x;
     const int s = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = tid & 63;
@@ -170,13 +173,13 @@ __device__ __forceinline__ void br_v4_body(V4Shared &sh, const V4Args &g, const 
         uint32_t x = t.xa ? (uint32_t)t.sa * (uint32_t)t.xa[i] : 0u;
         if (t.ya) x += (uint32_t)t.sb * (uint32_t)t.ya[i];
         if (t.za) x += (uint32_t)t.sc * (uint32_t)t.za[i];
-        sh.bara[i] = modswitch_2N(x);
+        sh.bara[i] = MANY ? modswitch_nu(x, mo.th) : modswitch_2N(x);
     }
     if (tid == 0) {
         uint32_t xb = (uint32_t)t.c + (t.xb ? (uint32_t)t.sa * (uint32_t)t.xb[0] : 0u);
         if (t.yb) xb += (uint32_t)t.sb * (uint32_t)t.yb[0];
         if (t.zb) xb += (uint32_t)t.sc * (uint32_t)t.zb[0];
-        sh.barb = modswitch_2N(xb);
+        sh.barb = MANY ? modswitch_nu(xb, mo.th) : modswitch_2N(xb);
     }
     __syncthreads();
     if (LUT && tv) {   // ACC = (0, X^{2N - barb} tv) as its periodic extension (modarith.h lut_coeff)
@@ -201,6 +204,13 @@ __device__ __forceinline__ void br_v4_body(V4Shared &sh, const V4Args &g, const 
     // sample extraction at index 0 (lwe.cu:41-56): a_j = -acc_a[N - j] = E_a[2N - j]
     for (int j = tid; j < kN; j += kV4Threads) ua[j] = (int32_t)sh.E[0][(k2N - j) & (k2N - 1)];
     if (tid == 0) *ub = (int32_t)sh.E[1][0];
+    if constexpr (MANY) {   // extraction at index f: a_j = E_a[(f - j) mod 2N], b = acc_b[f]
+        for (int f = 1; f < mo.n_out; ++f) {
+            int32_t *uf = mo.ua1 + (size_t)(f - 1) * mo.stride * kN;
+            for (int j = tid; j < kN; j += kV4Threads) uf[j] = (int32_t)sh.E[0][(f - j) & (k2N - 1)];
+        }
+        if (tid >= 1 && tid < mo.n_out) mo.ub1[(size_t)(tid - 1) * mo.stride] = (int32_t)sh.E[1][tid];
+    }
 }
 
 // Guard mode (engine.h Guard): the fp64 kernel ran first and flagged each ciphertext with its
@@ -226,7 +236,7 @@ __device__ __forceinline__ bool guard_skip(const V4Guard &gd, size_t slot) {
 // (tfhe_amd_select_kernel(4): 256 VGPRs, 27 spilled), 1 for the guard launch (284 VGPRs, no scratch: a
 // kernel with a private segment costs ~12 us more per dispatch even when every workgroup exits
 // at once)
-template <int MINW, bool LUT = false>
+template <int MINW, bool LUT = false, bool MANY = false>
 __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4(V4Args g, int B, int total, BrInput in0,
                                                                 BrInput in1, int32_t mu,
                                                                 int32_t *__restrict__ u_a,
@@ -245,7 +255,12 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4(V4Args g, 
         t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
         t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
         t.za = nullptr; t.zb = nullptr;
-        if constexpr (LUT)
+        if constexpr (MANY)   // one half: output f of ciphertext gct is u sample f B + gct
+            br_v4_body<true, true>(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct,
+                                   lut_table(in.tv, in.lut_index, in.n_lut, idx),
+                                   ManyOut{in.log_nu, in.n_out, u_a + ((size_t)B + gct) * kN, u_b + (size_t)B + gct,
+                                           (size_t)B});
+        else if constexpr (LUT)
             br_v4_body<true>(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct,
                              lut_table(in.tv, in.lut_index, in.n_lut, idx));
         else
@@ -255,7 +270,7 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4(V4Args g, 
 
 // circuit level: flat slot r B + k (row r, instance k < B), grid-stride as the gate kernel;
 // wires are [W][B] ciphertexts, the extracted sample of (r, k) goes to u slot r B + k
-template <int MINW, bool LUT = false>
+template <int MINW, bool LUT = false, bool MANY = false>
 __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4_rows(V4Args g, int B, long total,
                                                                      const CircRow *__restrict__ rows,
                                                                      const int32_t *__restrict__ wa,
@@ -281,7 +296,14 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4_rows(V4Arg
         wire(row.x, t.xa, t.xb);
         wire(row.y, t.ya, t.yb);
         wire(row.z, t.za, t.zb);
-        if constexpr (LUT) {
+        if constexpr (MANY) {
+            // outputs f >= 1 of a many-LUT row: u rows row.urow + f - 1 (engine.h CircRow)
+            const int32_t *tv = row.lut ? reinterpret_cast<const int32_t *>(rows + r) + row.lut : nullptr;
+            const size_t s1 = (size_t)row.urow * B + k;
+            br_v4_body<true, true>(sh, g, t, mu, u_a + (size_t)slot * kN, u_b + slot, tv,
+                                   ManyOut{row.many & 7, row.many ? (row.many >> 8) & 31 : 1, u_a + s1 * kN, u_b + s1,
+                                           (size_t)B});
+        } else if constexpr (LUT) {
             // a LUT row's test vector lies row.lut words after its own record (engine.h CircRow)
             const int32_t *tv = row.lut ? reinterpret_cast<const int32_t *>(rows + r) + row.lut : nullptr;
             br_v4_body<true>(sh, g, t, mu, u_a + (size_t)slot * kN, u_b + slot, tv);
@@ -398,6 +420,21 @@ hipError_t launch_blind_rotate_v4(const DeviceKey &key, int B, int halves, const
     // launch recomputes a flagged ciphertext from the same table
     const bool lut = in[0].tv != nullptr;
     if (lut != (in1.tv != nullptr) || (lut && (in[0].n_lut <= 0 || in1.n_lut <= 0))) return hipErrorInvalidValue;
+    // many-LUT (engine.h BrInput): one half, tables, log_nu in [0, 4], n_out in [1, 2^log_nu]
+    const bool many = in[0].n_out != 0;
+    if (many && (!lut || halves != 1 || in[0].log_nu < 0 || in[0].log_nu > 4 || in[0].n_out < 1 ||
+                 in[0].n_out > (1 << in[0].log_nu)))
+        return hipErrorInvalidValue;
+    if (many) {
+        trace_kernel(gd.flags ? "k_blind_rotate_v4(lut-many+guard)" : "k_blind_rotate_v4(lut-many)");
+        if (gd.flags)
+            hipLaunchKernelGGL((k_blind_rotate_v4<1, true, true>), dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B,
+                               total, in[0], in1, mu, u_a, u_b, gd);
+        else
+            hipLaunchKernelGGL((k_blind_rotate_v4<2, true, true>), dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B,
+                               total, in[0], in1, mu, u_a, u_b, gd);
+        return hipGetLastError();
+    }
     if (lut) {
         trace_kernel(gd.flags ? "k_blind_rotate_v4(lut+guard)" : "k_blind_rotate_v4(lut)");
         if (gd.flags)
@@ -426,6 +463,16 @@ hipError_t launch_blind_rotate_v4_rows(const DeviceKey &key, int B, int nrows, c
     const V4Guard gd = v4_guard(guard);
     const long total = (long)B * nrows;
     const long grid = gd.flags && total > kGuardGrid ? kGuardGrid : total < 0x7fffffffL ? total : 0x7fffffffL;
+    if (guard && guard->many_rows) {   // some row is a many-LUT row (engine.h Guard)
+        trace_kernel(gd.flags ? "k_blind_rotate_v4_rows(lut-many+guard)" : "k_blind_rotate_v4_rows(lut-many)");
+        if (gd.flags)
+            hipLaunchKernelGGL((k_blind_rotate_v4_rows<1, true, true>), dim3((unsigned)grid), dim3(kV4Threads), 0, s,
+                               v4_args(key), B, total, rows, wa, wb, mu, u_a, u_b, gd);
+        else
+            hipLaunchKernelGGL((k_blind_rotate_v4_rows<2, true, true>), dim3((unsigned)grid), dim3(kV4Threads), 0, s,
+                               v4_args(key), B, total, rows, wa, wb, mu, u_a, u_b, gd);
+        return hipGetLastError();
+    }
     if (guard && guard->lut_rows) {   // some row carries a test vector (engine.h Guard)
         trace_kernel(gd.flags ? "k_blind_rotate_v4_rows(lut+guard)" : "k_blind_rotate_v4_rows(lut)");
         if (gd.flags)

@@ -370,10 +370,14 @@ __device__ __forceinline__ void cmux_v6(V6Ct &sh, const double2 *shtw, const V6A
 // memory instead of the constant (mu, ..., mu); tv = null (a constant row of a rows launch that
 // also holds LUT rows) keeps the arithmetic initialisation.  Compile-time, so the constant
 // instantiations are untouched.
-template <int WAVES, bool RREG, int C = 1, bool PS = false, bool LUT = false>
+// MANY (many-LUT bootstrap; implies LUT): the prologue switches to a multiple of
+// 2^mo.th and the epilogue extracts the coefficients 0 .. mo.n_out - 1 (modarith.h ManyOut); the
+// 500 steps between them are the same.
+template <int WAVES, bool RREG, int C = 1, bool PS = false, bool LUT = false, bool MANY = false>
 __device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args &g, const RowTerms6 &t, int32_t mu,
                                            int32_t *__restrict__ ua, int32_t *__restrict__ ub, size_t slot,
-                                           bool live = true, const int32_t *__restrict__ tv = nullptr) {
+                                           bool live = true, const int32_t *__restrict__ tv = nullptr,
+                                           const ManyOut &mo = ManyOut{}) {
     const int tid = threadIdx.x & (kV6Threads - 1);
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = tid & 63;
@@ -391,13 +395,13 @@ __device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args
         uint32_t x = t.xa ? (uint32_t)t.sa * (uint32_t)t.xa[i] : 0u;
         if (t.ya) x += (uint32_t)t.sb * (uint32_t)t.ya[i];
         if (t.za) x += (uint32_t)t.sc * (uint32_t)t.za[i];
-        sh.bara[i] = (short)modswitch_2N(x);
+        sh.bara[i] = (short)(MANY ? modswitch_nu(x, mo.th) : modswitch_2N(x));
     }
     if (tid == 0) {
         uint32_t xb = (uint32_t)t.c + (t.xb ? (uint32_t)t.sa * (uint32_t)t.xb[0] : 0u);
         if (t.yb) xb += (uint32_t)t.sb * (uint32_t)t.yb[0];
         if (t.zb) xb += (uint32_t)t.sc * (uint32_t)t.zb[0];
-        sh.barb = modswitch_2N(xb);
+        sh.barb = MANY ? modswitch_nu(xb, mo.th) : modswitch_2N(xb);
     }
     if (tid < 2) sh.sync[tid] = 0;
     for (int e = threadIdx.x; e < kT8Words; e += C * kV6Threads) shtw[e] = g.tw[t8_src(e)];
@@ -470,8 +474,21 @@ __device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args
             const int j = L + 64 * r;
             ua[j] = (int32_t)E[(k2N - j) & (k2N - 1)];
         }
+        if constexpr (MANY) {
+            // extraction at index f: a_j = E_a[(f - j) mod 2N], from the extension written above
+            for (int f = 1; f < mo.n_out; ++f) {
+                int32_t *uf = mo.ua1 + (size_t)(f - 1) * mo.stride * kN;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int j = L + 64 * r;
+                    uf[j] = (int32_t)E[(f - j) & (k2N - 1)];
+                }
+            }
+        }
     } else if (L == 0) {
         *ub = (int32_t)acc[0];
+    } else if (MANY && L < mo.n_out) {   // lane f holds acc_b[f] in acc[0]
+        mo.ub1[(size_t)(L - 1) * mo.stride] = (int32_t)acc[0];
     }
 #ifdef TFHE_AMD_V6_STAMPS
     if (tid == 0 && wg < kWgSlots) {
@@ -481,7 +498,7 @@ __device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args
 #endif
 }
 
-template <int WAVES, bool RREG, bool LUT = false>
+template <int WAVES, bool RREG, bool LUT = false, bool MANY = false>
 __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6(V6Args g, int B, int base, BrInput in0,
                                                                 BrInput in1, int32_t mu, int32_t *__restrict__ u_a,
                                                                 int32_t *__restrict__ u_b) {
@@ -495,7 +512,12 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6(V6Args g,
     t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
     t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
     t.za = nullptr; t.zb = nullptr;
-    if constexpr (LUT)
+    if constexpr (MANY)   // one half: output f of ciphertext gct is u sample f B + gct
+        br_v6_body<WAVES, RREG, 1, false, true, true>(
+            sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct, true,
+            lut_table(in.tv, in.lut_index, in.n_lut, idx),
+            ManyOut{in.log_nu, in.n_out, u_a + ((size_t)B + gct) * kN, u_b + (size_t)B + gct, (size_t)B});
+    else if constexpr (LUT)
         br_v6_body<WAVES, RREG, 1, false, true>(sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct,
                                                 true, lut_table(in.tv, in.lut_index, in.n_lut, idx));
     else
@@ -505,7 +527,7 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6(V6Args g,
 // two ciphertexts per workgroup (4 waves): the dispatcher spreads a 4-wave workgroup over the
 // CU's 4 SIMDs, where two 2-wave workgroups sharing a CU land on 3 of them (2, 1, 1, 0 waves;
 // scripts/wave_placement.hip), so at B <= 2 CUs this keeps one wave per SIMD
-template <int WAVES, bool PS = false, bool LUT = false>
+template <int WAVES, bool PS = false, bool LUT = false, bool MANY = false>
 __global__ __launch_bounds__(2 * kV6Threads, WAVES) void k_blind_rotate_v6p(V6Args g, int B, int total, int base,
                                                                      BrInput in0, BrInput in1, int32_t mu,
                                                                      int32_t *__restrict__ u_a,
@@ -524,14 +546,19 @@ __global__ __launch_bounds__(2 * kV6Threads, WAVES) void k_blind_rotate_v6p(V6Ar
     t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
     t.za = nullptr; t.zb = nullptr;
     // (the padding ciphertext repeats the last live one, table included)
-    if constexpr (LUT)
+    if constexpr (MANY)
+        br_v6_body<WAVES, true, 2, PS, true, true>(
+            sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct, live,
+            lut_table(in.tv, in.lut_index, in.n_lut, idx),
+            ManyOut{in.log_nu, in.n_out, u_a + ((size_t)B + gct) * kN, u_b + (size_t)B + gct, (size_t)B});
+    else if constexpr (LUT)
         br_v6_body<WAVES, true, 2, PS, true>(sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct,
                                              live, lut_table(in.tv, in.lut_index, in.n_lut, idx));
     else
         br_v6_body<WAVES, true, 2, PS>(sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct, live);
 }
 
-template <int WAVES, bool RREG, bool LUT = false>
+template <int WAVES, bool RREG, bool LUT = false, bool MANY = false>
 __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6_rows(V6Args g, int B, long base,
                                                                      const CircRow *__restrict__ rows,
                                                                      const int32_t *__restrict__ wa,
@@ -554,7 +581,15 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6_rows(V6Ar
     wire(row.y, t.ya, t.yb);
     wire(row.z, t.za, t.zb);
     const size_t slot = (size_t)r * B + k;
-    if constexpr (LUT) {
+    if constexpr (MANY) {
+        // outputs f >= 1 of a many-LUT row: u rows row.urow + f - 1 (engine.h CircRow); every other
+        // row of the launch is th = 0, n_out = 1
+        const int32_t *tv = row.lut ? reinterpret_cast<const int32_t *>(rows + r) + row.lut : nullptr;
+        const size_t s1 = (size_t)row.urow * B + k;
+        br_v6_body<WAVES, RREG, 1, false, true, true>(
+            sh.ct[0], sh.tw, g, t, mu, u_a + slot * kN, u_b + slot, slot, true, tv,
+            ManyOut{row.many & 7, row.many ? (row.many >> 8) & 31 : 1, u_a + s1 * kN, u_b + s1, (size_t)B});
+    } else if constexpr (LUT) {
         // a LUT row's test vector lies row.lut words after its own record (engine.h CircRow)
         const int32_t *tv = row.lut ? reinterpret_cast<const int32_t *>(rows + r) + row.lut : nullptr;
         br_v6_body<WAVES, RREG, 1, false, true>(sh.ct[0], sh.tw, g, t, mu, u_a + slot * kN, u_b + slot, slot, true, tv);
@@ -743,6 +778,38 @@ static V6Args v6_args(const DeviceKey &key, long wgs, const Guard *guard = nullp
     return g;
 }
 
+// one chunk of a programmable-bootstrap launch: the constant path's launch forms, LUT (MANY:
+// many-LUT) instantiations
+template <bool MANY>
+static void v6_launch_lut(const DeviceKey &key, long n, int B, long total, long base, const BrInput &in0,
+                          const BrInput &in1, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
+                          const Guard *guard) {
+    if (v6_pair(key, n)) {
+        const long wgs = (n + 1) / 2;
+        if (v6p_pairsync() && guard && guard->flags) {
+            trace_kernel(MANY ? "k_blind_rotate_v6p(lut-many+paired+reg-rotation+pair-sync)"
+                              : "k_blind_rotate_v6p(lut+paired+reg-rotation+pair-sync)");
+            hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, true, true, MANY>), dim3((unsigned)wgs),
+                               dim3(2 * kV6Threads), 0, s, v6_args(key, wgs, guard, true), B, (int)total, (int)base,
+                               in0, in1, mu, u_a, u_b);
+        } else {
+            trace_kernel(MANY ? "k_blind_rotate_v6p(lut-many+paired+reg-rotation)"
+                              : "k_blind_rotate_v6p(lut+paired+reg-rotation)");
+            hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, false, true, MANY>), dim3((unsigned)wgs),
+                               dim3(2 * kV6Threads), 0, s, v6_args(key, wgs, guard, true), B, (int)total, (int)base,
+                               in0, in1, mu, u_a, u_b);
+        }
+    } else if (v6_rreg(key, n)) {
+        trace_kernel(MANY ? "k_blind_rotate_v6(lut-many+reg-rotation)" : "k_blind_rotate_v6(lut+reg-rotation)");
+        hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, true, true, MANY>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
+                           v6_args(key, n, guard), B, (int)base, in0, in1, mu, u_a, u_b);
+    } else {
+        trace_kernel(MANY ? "k_blind_rotate_v6(lut-many+lds-rotation)" : "k_blind_rotate_v6(lut+lds-rotation)");
+        hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, false, true, MANY>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
+                           v6_args(key, n, guard), B, (int)base, in0, in1, mu, u_a, u_b);
+    }
+}
+
 hipError_t launch_blind_rotate_v6(const DeviceKey &key, int B, int halves, const BrInput *in, int32_t mu,
                                   int32_t *u_a, int32_t *u_b, hipStream_t s, const Guard *guard) {
     if (B <= 0) return hipSuccess;
@@ -752,32 +819,16 @@ hipError_t launch_blind_rotate_v6(const DeviceKey &key, int B, int halves, const
     // programmable bootstrap: every half carries its tables (n_lut >= 1), or none does
     const bool lut = in[0].tv != nullptr;
     if (lut != (in1.tv != nullptr) || (lut && (in[0].n_lut <= 0 || in1.n_lut <= 0))) return hipErrorInvalidValue;
+    // many-LUT (engine.h BrInput): one half, tables, log_nu in [0, 4], n_out in [1, 2^log_nu]
+    const bool many = in[0].n_out != 0;
+    if (many && (!lut || halves != 1 || in[0].log_nu < 0 || in[0].log_nu > 4 || in[0].n_out < 1 ||
+                 in[0].n_out > (1 << in[0].log_nu)))
+        return hipErrorInvalidValue;
     for (long base = 0; base < total; base += chunk) {
         const long n = total - base < chunk ? total - base : chunk;
         if (lut) {
-            // the constant path's launch forms, LUT instantiations
-            if (v6_pair(key, n)) {
-                const long wgs = (n + 1) / 2;
-                if (v6p_pairsync() && guard && guard->flags) {
-                    trace_kernel("k_blind_rotate_v6p(lut+paired+reg-rotation+pair-sync)");
-                    hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, true, true>), dim3((unsigned)wgs),
-                                       dim3(2 * kV6Threads), 0, s, v6_args(key, wgs, guard, true), B, (int)total,
-                                       (int)base, in[0], in1, mu, u_a, u_b);
-                } else {
-                    trace_kernel("k_blind_rotate_v6p(lut+paired+reg-rotation)");
-                    hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, false, true>), dim3((unsigned)wgs),
-                                       dim3(2 * kV6Threads), 0, s, v6_args(key, wgs, guard, true), B, (int)total,
-                                       (int)base, in[0], in1, mu, u_a, u_b);
-                }
-            } else if (v6_rreg(key, n)) {
-                trace_kernel("k_blind_rotate_v6(lut+reg-rotation)");
-                hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, true, true>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
-                                   v6_args(key, n, guard), B, (int)base, in[0], in1, mu, u_a, u_b);
-            } else {
-                trace_kernel("k_blind_rotate_v6(lut+lds-rotation)");
-                hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, false, true>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
-                                   v6_args(key, n, guard), B, (int)base, in[0], in1, mu, u_a, u_b);
-            }
+            if (many) v6_launch_lut<true>(key, n, B, total, base, in[0], in1, mu, u_a, u_b, s, guard);
+            else v6_launch_lut<false>(key, n, B, total, base, in[0], in1, mu, u_a, u_b, s, guard);
         } else if (v6_pair(key, n)) {
             const long wgs = (n + 1) / 2;
             // the pair sync's bounded poll hands a ciphertext whose partner never arrives to the
@@ -813,6 +864,17 @@ hipError_t launch_blind_rotate_v6_rows(const DeviceKey &key, int B, int nrows, c
     for (long base = 0; base < total; base += chunk) {
         const long n = total - base < chunk ? total - base : chunk;
         if (n > 0x7fffffffL) return hipErrorInvalidValue;
+        if (guard && guard->many_rows) {   // some row is a many-LUT row (engine.h Guard)
+            trace_kernel(v6_rreg(key, n) ? "k_blind_rotate_v6_rows(lut-many+reg-rotation)"
+                                         : "k_blind_rotate_v6_rows(lut-many+lds-rotation)");
+            if (v6_rreg(key, n))
+                hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, true, true, true>), dim3((unsigned)n),
+                                   dim3(kV6Threads), 0, s, v6_args(key, n, guard), B, base, rows, wa, wb, mu, u_a, u_b);
+            else
+                hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, false, true, true>), dim3((unsigned)n),
+                                   dim3(kV6Threads), 0, s, v6_args(key, n, guard), B, base, rows, wa, wb, mu, u_a, u_b);
+            continue;
+        }
         if (guard && guard->lut_rows) {   // some row carries a test vector (engine.h Guard)
             trace_kernel(v6_rreg(key, n) ? "k_blind_rotate_v6_rows(lut+reg-rotation)"
                                          : "k_blind_rotate_v6_rows(lut+lds-rotation)");

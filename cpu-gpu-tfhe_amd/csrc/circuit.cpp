@@ -41,8 +41,13 @@ struct Node {
     int32_t s[3];        // lincomb coefficients
     int in[3];           // input wires (-1 = absent)
     int table = -1;      // programmable-bootstrap node (gate kLutGate): its test vector's table id
+    // many-LUT node (gate kManyGate): n_out consecutive wires, one Node each, that share one
+    // bootstrapped row; index = the wire's position in the node (the extraction index)
+    int log_nu = 0, n_out = 1, index = 0;
 };
 constexpr int kLutGate = -2;   // gate code of a LUT node (tfhe_amd_circuit_node)
+constexpr int kManyGate = -3;  // gate code of every wire of a many-LUT node
+constexpr int kExtraRow = 1 << 30;   // compile: a u row behind the level's rows, until their number is known
 
 struct Affine {          // W = (0, c) + s W[base]; base = -1: the trivial sample (0, c)
     int32_t c, s;
@@ -78,7 +83,9 @@ struct TfheAmdCircuit {
     std::vector<Node> nodes;           // one per wire
     // compiled schedule
     bool compiled = false;
-    struct Level { int row0, nrows, ks0, nks, lin0, nlin; bool lut; };   // lut: some row carries a test vector
+    // lut: some row carries a test vector; many: some row is a many-LUT row; urows: u rows the
+    // level writes (nrows + the further outputs of its many-LUT rows)
+    struct Level { int row0, nrows, ks0, nks, lin0, nlin; bool lut; bool many = false; int urows = 0; };
     std::vector<Level> levels;         // levels[0]: affine nodes over inputs only
     std::vector<CircRow> rows;
     std::vector<CircKs> ks;
@@ -86,7 +93,7 @@ struct TfheAmdCircuit {
     // programmable-bootstrap test vectors [n][kN]; uploaded behind the level tables, where the LUT
     // rows find them by a self-relative offset (engine.h CircRow.lut)
     std::vector<int32_t> luts;
-    int n_boot = 0, max_rows = 0;
+    int n_boot = 0, max_rows = 0;   // max_rows: the largest level's u rows
     // per executing context (keyed by the context): device tables + scratch
     std::mutex mu;   // compile + the state map; runs on distinct contexts proceed concurrently
     // keyed by the context's uid (engine.cpp; never reused), dropped when the context is destroyed
@@ -176,8 +183,9 @@ int compile(TfheAmdCircuit *C) {
     std::vector<std::vector<CircRow>> rows;
     std::vector<std::vector<CircKs>> kss;
     std::vector<std::vector<CircLin>> lins;
+    std::vector<int> extras;   // per level: u rows behind the level's rows (many-LUT outputs f >= 1)
     auto ensure = [&](int L) {
-        if ((int)rows.size() <= L) { rows.resize(L + 1); kss.resize(L + 1); lins.resize(L + 1); }
+        if ((int)rows.size() <= L) { rows.resize(L + 1); kss.resize(L + 1); lins.resize(L + 1); extras.resize(L + 1, 0); }
     };
     ensure(0);
     C->n_boot = 0;
@@ -198,6 +206,11 @@ int compile(TfheAmdCircuit *C) {
             level[w] = a.base < 0 ? 0 : level[a.base];
             ensure(level[w]);
             lins[level[w]].push_back(CircLin{a.c, a.s, a.base, w});
+            continue;
+        }
+        if (nd.gate == kManyGate && nd.index > 0) {   // a further output of the row its first wire made
+            level[w] = level[w - nd.index];
+            aff[w] = Affine{0, 1, w};
             continue;
         }
         // bootstrapped
@@ -228,9 +241,18 @@ int compile(TfheAmdCircuit *C) {
         } else {
             CircRow r;
             build_row(nd.c0, nd.s, A, 3, &r);
-            if (nd.gate == kLutGate) r.lut = nd.table + 1;   // table id + 1 until the layout is known (below)
+            // table id + 1 until the layout is known (below)
+            if (nd.gate == kLutGate || nd.gate == kManyGate) r.lut = nd.table + 1;
+            if (nd.gate == kManyGate) {
+                r.many = nd.log_nu | nd.n_out << 8;
+                r.urow = kExtraRow + extras[L];   // level-relative until the level's rows are known (below)
+            }
             R.push_back(r);
             kss[L].push_back(CircKs{(int)R.size() - 1, -1, 0, w});
+            if (nd.gate == kManyGate) {   // the node's further wires: the level's one key switch reads their u rows
+                if (w + nd.n_out > W) return TFHE_AMD_E_ARG;
+                for (int f = 1; f < nd.n_out; ++f) kss[L].push_back(CircKs{kExtraRow + extras[L]++, -1, 0, w + f});
+            }
             C->n_boot += 1;
         }
     }
@@ -239,13 +261,20 @@ int compile(TfheAmdCircuit *C) {
     for (size_t L = 0; L < rows.size(); ++L) {
         TfheAmdCircuit::Level lv{(int)C->rows.size(), (int)rows[L].size(), (int)C->ks.size(), (int)kss[L].size(),
                                  (int)C->lin.size(), (int)lins[L].size(), false};
-        if (lv.nrows > 65535) return TFHE_AMD_E_ARG;
-        for (const CircRow &r : rows[L]) lv.lut = lv.lut || r.lut != 0;
+        lv.urows = lv.nrows + extras[L];
+        if (lv.urows > 65535) return TFHE_AMD_E_ARG;
+        for (CircRow &r : rows[L]) {
+            lv.lut = lv.lut || r.lut != 0;
+            lv.many = lv.many || r.many != 0;
+            if (r.many) r.urow = lv.nrows + (r.urow - kExtraRow);
+        }
+        for (CircKs &k : kss[L])
+            if (k.r1 >= kExtraRow) k.r1 = lv.nrows + (k.r1 - kExtraRow);
         C->rows.insert(C->rows.end(), rows[L].begin(), rows[L].end());
         C->ks.insert(C->ks.end(), kss[L].begin(), kss[L].end());
         C->lin.insert(C->lin.end(), lins[L].begin(), lins[L].end());
         C->levels.push_back(lv);
-        C->max_rows = std::max(C->max_rows, lv.nrows);
+        C->max_rows = std::max(C->max_rows, lv.urows);
     }
     // a LUT row's test vector: words from the row's own record to its table in the uploaded block
     // [rows | ks | lin | tables] (tfhe_amd_circuit_run_dev_impl)
@@ -350,6 +379,33 @@ extern "C" int tfhe_amd_circuit_lut(TfheAmdCircuit *c, int table, int32_t c0, in
     return add_node(c, n);
 }
 
+// Many-LUT node: one bootstrapped row, n_out consecutive wires
+extern "C" int tfhe_amd_circuit_lut_many(TfheAmdCircuit *c, int table, int log_nu, int n_out, int32_t c0, int32_t sa,
+                                         int a, int32_t sb, int b, int32_t sc, int cc) {
+    if (!c || a < 0 || table < 0 || (size_t)table >= c->luts.size() / kN) return TFHE_AMD_E_ARG;
+    if (log_nu < 0 || log_nu > 4 || n_out < 1 || n_out > (1 << log_nu)) return TFHE_AMD_E_ARG;
+    Node n{1, kManyGate, c0, {sa, b >= 0 ? sb : 0, cc >= 0 ? sc : 0}, {a, b, cc}, table, log_nu, n_out, 0};
+    const int first = add_node(c, n);
+    if (first < 0) return first;
+    for (int f = 1; f < n_out; ++f) {
+        n.index = f;
+        c->nodes.push_back(n);
+    }
+    return first;
+}
+
+extern "C" int tfhe_amd_circuit_lut_many_node(const TfheAmdCircuit *c, int w, int *table, int32_t *c0, int *log_nu,
+                                              int *n_out, int *index) {
+    if (!c || w < 0 || w >= (int)c->nodes.size() || c->nodes[w].gate != kManyGate) return TFHE_AMD_E_ARG;
+    const Node &n = c->nodes[w];
+    if (table) *table = n.table;
+    if (c0) *c0 = n.c0;
+    if (log_nu) *log_nu = n.log_nu;
+    if (n_out) *n_out = n.n_out;
+    if (index) *index = n.index;
+    return TFHE_AMD_OK;
+}
+
 extern "C" int tfhe_amd_circuit_lut_node(const TfheAmdCircuit *c, int w, int *table, int32_t *c0) {
     if (!c || w < 0 || w >= (int)c->nodes.size() || c->nodes[w].gate != kLutGate) return TFHE_AMD_E_ARG;
     if (table) *table = c->nodes[w].table;
@@ -363,7 +419,8 @@ extern "C" int tfhe_amd_circuit_node(const TfheAmdCircuit *c, int w, int *kind, 
     const Node &n = c->nodes[w];
     if (kind) *kind = n.kind;
     if (gate) *gate = n.gate;
-    if (c0) *c0 = n.gate == kLutGate ? n.table : n.c0;   // a LUT node: the table id (tfhe_amd_circuit_lut_node)
+    // a LUT / many-LUT node: the table id (tfhe_amd_circuit_lut_node, tfhe_amd_circuit_lut_many_node)
+    if (c0) *c0 = n.gate == kLutGate || n.gate == kManyGate ? n.table : n.c0;
     for (int t = 0; t < 3; ++t) {
         if (s) s[t] = n.s[t];
         if (in) in[t] = n.in[t];
@@ -380,7 +437,7 @@ extern "C" int tfhe_amd_circuit_info(TfheAmdCircuit *c, int *n_wires, int *n_gat
         if (rc != TFHE_AMD_OK) return rc;
     }
     int ng = 0;
-    for (const Node &n : c->nodes) ng += n.kind != 0;
+    for (const Node &n : c->nodes) ng += n.kind != 0 && n.index == 0;   // a many-LUT node counts once
     if (n_wires) *n_wires = (int)c->nodes.size();
     if (n_gates) *n_gates = ng;
     if (n_bootstraps) *n_bootstraps = c->n_boot;
@@ -456,6 +513,7 @@ int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int de
         if (lv.nrows) {
             Guard gd = guard_stats ? Guard{st->u_flags, guard_stats} : Guard{};
             gd.lut_rows = lv.lut;   // the launch takes the rows kernels' LUT instantiation
+            gd.many_rows = lv.many;  // ... or their many-LUT instantiation
             const hipError_t e =
                 launch_blind_rotate_rows(key, B, lv.nrows, d_rows + lv.row0, wa, wb, kE8, st->u_a, st->u_b, s, &gd);
             if (e != hipSuccess) return TFHE_AMD_E_HIP;

@@ -134,7 +134,8 @@ hipError_t launch_blind_rotate_rows(const DeviceKey &key, int B, int nrows, cons
                                     const Guard *guard) {
     switch (br_version()) {
     case 4: {
-        const Guard lut_only{nullptr, nullptr, true};   // no flags: not guard mode, LUT rows present
+        // no flags: not guard mode, LUT (many-LUT) rows present
+        const Guard lut_only{nullptr, nullptr, true, guard && guard->many_rows};
         return launch_blind_rotate_v4_rows(key, B, nrows, rows, wa, wb, mu, u_a, u_b, s,
                                            guard && guard->lut_rows ? &lut_only : nullptr);
     }
@@ -705,12 +706,35 @@ extern "C" int tfhe_amd_lut_fill(int32_t *tv, int p, const int32_t *values) {
     return TFHE_AMD_OK;
 }
 
+// many-LUT test vector: function j mod nu at coefficient j, zero where
+// j mod nu >= n_fn
+extern "C" int tfhe_amd_lut_fill_many(int32_t *tv, int p, int log_nu, int n_fn, const int32_t *values) {
+    if (!tv || !values || p < 1 || p > kN || (p & (p - 1)) || log_nu < 0 || log_nu > 4) return TFHE_AMD_E_ARG;
+    const int nu = 1 << log_nu;
+    if (n_fn < 1 || n_fn > nu || (long)p * nu > kN) return TFHE_AMD_E_ARG;
+    for (int j = 0; j < kN; ++j) {
+        const int f = j & (nu - 1);
+        tv[j] = f < n_fn ? values[(size_t)f * p + (int)(((long)j * p) >> kLogN)] : 0;
+    }
+    return TFHE_AMD_OK;
+}
+
+static bool many_args_ok(int log_nu, int n_out) {
+    return log_nu >= 0 && log_nu <= 4 && n_out >= 1 && n_out <= (1 << log_nu);
+}
+
 // B bootstraps of (0, c) + sa X + sb Y through the tables tv [n_lut][kN] (engine.h BrInput); ks:
-// followed by the key switch into out (n = 500), else out is the extracted sample (N = 1024)
+// followed by the key switch into out (n = 500), else out is the extracted sample (N = 1024).
+// n_out >= 1: the many-LUT form (engine.h BrInput), n_out B samples out, function-major; n_out = 0:
+// the single-table form
 static int lut_batch_dev(TfheAmdContext *c, bool ks, int B, int n_lut, const int32_t *tv, const int32_t *lut_index,
                          int32_t cst, int32_t sa, const int32_t *x_a, const int32_t *x_b, int32_t sb,
-                         const int32_t *y_a, const int32_t *y_b, int32_t *out_a, int32_t *out_b, void *stream) {
+                         const int32_t *y_a, const int32_t *y_b, int32_t *out_a, int32_t *out_b, void *stream,
+                         int log_nu = 0, int n_out = 0) {
     if (!c || B < 0 || n_lut <= 0 || !tv || !c->key.has_bk || (ks && !c->key.ksk)) return TFHE_AMD_E_ARG;
+    if (n_out != 0 && !many_args_ok(log_nu, n_out)) return TFHE_AMD_E_ARG;
+    const int n_res = n_out ? n_out : 1;
+    if ((long)B * n_res > 0x3fffffffL) return TFHE_AMD_E_ARG;
     if (B == 0) return TFHE_AMD_OK;
     if (!x_a || !x_b || !out_a || !out_b || (sb && (!y_a || !y_b))) return TFHE_AMD_E_ARG;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
@@ -718,10 +742,11 @@ static int lut_batch_dev(TfheAmdContext *c, bool ks, int B, int n_lut, const int
     DeviceScope dev_scope(c->device);
     HIPCHK(dev_scope.rc);
     TraceScope trace(c);
-    int rc = tfhe_amd_reserve(c, B);   // guard flags (and the extracted samples) live in the context's scratch
+    // guard flags (per ciphertext) and the extracted samples (per output) live in the context's scratch
+    int rc = tfhe_amd_reserve(c, B * n_res);
     if (rc) return rc;
     HIPCHK(c->fence.acquire(s));
-    BrInput in{x_a, x_b, sb ? y_a : nullptr, sb ? y_b : nullptr, cst, sa, sb, n_lut, tv, lut_index};
+    BrInput in{x_a, x_b, sb ? y_a : nullptr, sb ? y_b : nullptr, cst, sa, sb, n_lut, tv, lut_index, log_nu, n_out};
     {
         ProfScope ps(c, s, true);
         const Guard gd = ctx_guard(c);
@@ -729,10 +754,30 @@ static int lut_batch_dev(TfheAmdContext *c, bool ks, int B, int n_lut, const int
     }
     if (ks) {
         ProfScope ps(c, s, false);
-        HIPCHK(launch_keyswitch(c->key, B, c->u_a, c->u_b, nullptr, nullptr, 0, out_a, out_b, s));
+        HIPCHK(launch_keyswitch(c->key, B * n_res, c->u_a, c->u_b, nullptr, nullptr, 0, out_a, out_b, s));
     }
     HIPCHK(c->fence.done(s));
     return TFHE_AMD_OK;
+}
+
+extern "C" int tfhe_amd_bootstrap_lut_many_woks_batch_dev(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,
+                                                          const int32_t *lut_index, int log_nu, int n_out,
+                                                          int32_t cst, int32_t sa, const int32_t *x_a,
+                                                          const int32_t *x_b, int32_t sb, const int32_t *y_a,
+                                                          const int32_t *y_b, int32_t *u_a, int32_t *u_b,
+                                                          void *stream) {
+    if (!many_args_ok(log_nu, n_out)) return TFHE_AMD_E_ARG;
+    return lut_batch_dev(c, false, B, n_lut, tv, lut_index, cst, sa, x_a, x_b, sb, y_a, y_b, u_a, u_b, stream, log_nu,
+                         n_out);
+}
+extern "C" int tfhe_amd_bootstrap_lut_many_batch_dev(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,
+                                                     const int32_t *lut_index, int log_nu, int n_out, int32_t cst,
+                                                     int32_t sa, const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                                     const int32_t *y_a, const int32_t *y_b, int32_t *res_a,
+                                                     int32_t *res_b, void *stream) {
+    if (!many_args_ok(log_nu, n_out)) return TFHE_AMD_E_ARG;
+    return lut_batch_dev(c, true, B, n_lut, tv, lut_index, cst, sa, x_a, x_b, sb, y_a, y_b, res_a, res_b, stream,
+                         log_nu, n_out);
 }
 
 extern "C" int tfhe_amd_bootstrap_lut_woks_batch_dev(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,
@@ -1525,8 +1570,11 @@ extern "C" int tfhe_amd_keyswitch_batch_host(TfheAmdContext *c, int B, const int
 // (n_lut x 4 KB) and the table indices uploaded beside the inputs (in-place safe)
 static int lut_batch_host(TfheAmdContext *c, bool ks, int B, int n_lut, const int32_t *tv, const int32_t *lut_index,
                           int32_t cst, int32_t sa, const int32_t *x_a, const int32_t *x_b, int32_t sb,
-                          const int32_t *y_a, const int32_t *y_b, int32_t *out_a, int32_t *out_b) {
+                          const int32_t *y_a, const int32_t *y_b, int32_t *out_a, int32_t *out_b, int log_nu = 0,
+                          int n_out = 0) {
     if (!c || B < 0 || n_lut <= 0 || !tv) return TFHE_AMD_E_ARG;
+    if (n_out != 0 && !many_args_ok(log_nu, n_out)) return TFHE_AMD_E_ARG;
+    const size_t n_res = n_out ? n_out : 1;   // outputs per ciphertext, function-major in out
     if (lut_index)
         for (int i = 0; i < B; ++i)
             if (lut_index[i] < 0 || lut_index[i] >= n_lut) return TFHE_AMD_E_ARG;
@@ -1534,15 +1582,15 @@ static int lut_batch_host(TfheAmdContext *c, bool ks, int B, int n_lut, const in
     if (!x_a || !x_b || !out_a || !out_b || (sb && (!y_a || !y_b))) return TFHE_AMD_E_ARG;
     // [x_a | x_b | y_a | y_b | tables | indices | out_a | out_b] in the io scratch (4 cap x 501 words)
     const int dout = ks ? kn : kN;
-    const size_t Ai = (size_t)B * kn, Ao = (size_t)B * dout, Tw = (size_t)n_lut * kN;
+    const size_t Ai = (size_t)B * kn, Ao = n_res * B * dout, Bo = n_res * B, Tw = (size_t)n_lut * kN;
     const size_t o_y = Ai + B, o_tv = o_y + (sb ? Ai + B : 0), o_ix = o_tv + Tw, o_out = o_ix + (lut_index ? B : 0);
-    const size_t need = o_out + Ao + B, cap = (need + io_words(1) - 1) / io_words(1);
+    const size_t need = o_out + Ao + Bo, cap = (need + io_words(1) - 1) / io_words(1);
     if (cap > ((size_t)1 << 24)) return TFHE_AMD_E_ARG;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     DeviceScope dev_scope(c->device);
     HIPCHK(dev_scope.rc);
     TraceScope trace(c);
-    int rc = tfhe_amd_reserve(c, std::max(B, (int)cap));
+    int rc = tfhe_amd_reserve(c, std::max((int)Bo, (int)cap));
     if (rc) return rc;
     int32_t *h = c->h_io, *d = c->io;
     memcpy(h, x_a, Ai * 4);
@@ -1556,13 +1604,31 @@ static int lut_batch_host(TfheAmdContext *c, bool ks, int B, int n_lut, const in
     HIPCHK(hipMemcpyAsync(d, h, o_out * 4, hipMemcpyHostToDevice, c->stream));
     int32_t *oa = d + o_out, *ob = oa + Ao;
     rc = lut_batch_dev(c, ks, B, n_lut, d + o_tv, lut_index ? d + o_ix : nullptr, cst, sa, d, d + Ai, sb,
-                       sb ? d + o_y : nullptr, sb ? d + o_y + Ai : nullptr, oa, ob, c->stream);
+                       sb ? d + o_y : nullptr, sb ? d + o_y + Ai : nullptr, oa, ob, c->stream, log_nu, n_out);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h + o_out, oa, (Ao + B) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h + o_out, oa, (Ao + Bo) * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(out_a, h + o_out, Ao * 4);
-    memcpy(out_b, h + o_out + Ao, (size_t)B * 4);
+    memcpy(out_b, h + o_out + Ao, Bo * 4);
     return TFHE_AMD_OK;
+}
+
+extern "C" int tfhe_amd_bootstrap_lut_many_woks_batch_host(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,
+                                                           const int32_t *lut_index, int log_nu, int n_out,
+                                                           int32_t cst, int32_t sa, const int32_t *x_a,
+                                                           const int32_t *x_b, int32_t sb, const int32_t *y_a,
+                                                           const int32_t *y_b, int32_t *u_a, int32_t *u_b) {
+    if (!many_args_ok(log_nu, n_out)) return TFHE_AMD_E_ARG;
+    return lut_batch_host(c, false, B, n_lut, tv, lut_index, cst, sa, x_a, x_b, sb, y_a, y_b, u_a, u_b, log_nu, n_out);
+}
+extern "C" int tfhe_amd_bootstrap_lut_many_batch_host(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,
+                                                      const int32_t *lut_index, int log_nu, int n_out, int32_t cst,
+                                                      int32_t sa, const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                                      const int32_t *y_a, const int32_t *y_b, int32_t *res_a,
+                                                      int32_t *res_b) {
+    if (!many_args_ok(log_nu, n_out)) return TFHE_AMD_E_ARG;
+    return lut_batch_host(c, true, B, n_lut, tv, lut_index, cst, sa, x_a, x_b, sb, y_a, y_b, res_a, res_b, log_nu,
+                          n_out);
 }
 
 extern "C" int tfhe_amd_bootstrap_lut_woks_batch_host(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,

@@ -35,6 +35,10 @@ constexpr int kTw6Words = 4 + 4 * 4 * 64 + 8 * 64 + 2 * 64;   // fft_wave.h tabl
 // launchers pick the kernels' LUT instantiation.  tv = [n_lut][kN] on the device; ciphertext g
 // takes table t = lut_index[g] (null: table 0), clamped by the kernel into [0, n_lut) before any
 // address is formed.  The launchers' mu is unused then.
+// Many-LUT bootstrap: n_out >= 1 picks the kernels' many-LUT instantiation (one
+// half only).  The prologue switches to a multiple of nu = 2^log_nu and the epilogue extracts the
+// coefficients f = 0 .. n_out - 1 of the rotated accumulator; output f of ciphertext g goes to u
+// sample f B + g, so u holds n_out B samples.  n_out = 0: the single-table launch above.
 struct BrInput {
     const int32_t *x_a, *x_b;
     const int32_t *y_a, *y_b;
@@ -42,6 +46,7 @@ struct BrInput {
     int32_t n_lut = 0;
     const int32_t *tv = nullptr;
     const int32_t *lut_index = nullptr;
+    int32_t log_nu = 0, n_out = 0;
 };
 
 // One bootstrapped row of a circuit level (circuit.cpp): the blind rotation input is
@@ -50,9 +55,13 @@ struct BrInput {
 // starts `lut` 32-bit words after the row's own record, in the same device allocation (the level
 // tables and the circuit's LUT tables are uploaded as one block, so the offset is the same on every
 // device).  Only launches whose Guard says lut_rows read it.
+// many (launches whose Guard says many_rows): 0 = one output; otherwise log_nu | n_out << 8 of a
+// many-LUT row.  Output 0 of row r goes to u row r like every row's; outputs
+// f >= 1 go to the u rows urow + f - 1, which lie behind the level's nrows rows.
 struct CircRow {
     int32_t c, sa, sb, sc;
     int32_t x, y, z, lut;
+    int32_t many = 0, urow = 0;
 };
 // One key-switched circuit output: W[out] = KS(u[r1] (+ u[r2] if r2 >= 0) + (0, add_b)).
 struct CircKs {
@@ -116,10 +125,13 @@ struct StreamFence {
 // lut_rows (rows launches only): some row of the level carries a test vector (CircRow.lut), so
 // the rows launchers take the kernels' LUT instantiation; it rides here because the row records
 // themselves are in device memory.  With flags null it is the only thing the struct says.
+// many_rows (rows launches only, implies lut_rows): some row is a many-LUT row (CircRow.many), so
+// the launchers take the many-LUT instantiation.  The flags stay per row x instance.
 struct Guard {
     uint32_t *flags = nullptr;
     uint32_t *stats = nullptr;
     bool lut_rows = false;
+    bool many_rows = false;
 };
 uint32_t guard_threshold_hi();
 

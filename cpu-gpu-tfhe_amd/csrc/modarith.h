@@ -59,6 +59,21 @@ __device__ __forceinline__ int modswitch_2N(uint32_t x) {
     return (int)((((uint64_t)x + (1u << 20)) >> 21) & (k2N - 1));
 }
 
+// Many-LUT bootstrap: the modulus switch to a multiple of nu = 2^th,
+// nu * modSwitchFromTorus32(x, 2N / nu) mod 2N, with the same wrap: phases in
+// [2^32 - 2^(20 + th), 2^32) give 0.  th = 0 is modswitch_2N.
+__device__ __forceinline__ int modswitch_nu(uint32_t x, int th) {
+    return (int)(((((uint64_t)x + ((uint64_t)1 << (20 + th))) >> (21 + th)) << th) & (k2N - 1));
+}
+
+// Where the epilogue of a many-LUT launch writes: output 0 goes where a single extraction goes,
+// output f >= 1 to sample (f - 1) * stride behind (ua1, ub1).  th = log_nu.
+struct ManyOut {
+    int th = 0, n_out = 1;
+    int32_t *ua1 = nullptr, *ub1 = nullptr;
+    size_t stride = 0;
+};
+
 // Programmable bootstrap (engine.h BrInput), both kernel generations.
 // The test vector of ciphertext idx out of tv [n_lut][kN]: the index comes from device memory
 // unchecked by the host, so it is clamped into [0, n_lut) before it forms an address.

@@ -80,6 +80,13 @@ def _load():
     for f in ("tfhe_amd_bootstrap_lut_woks_batch_host", "tfhe_amd_bootstrap_lut_batch_host"):
         getattr(L, f).argtypes = ([_VP, ctypes.c_int, ctypes.c_int, _I32P, _I32P, ctypes.c_int32, ctypes.c_int32, _I32P,
                                    _I32P, ctypes.c_int32] + [_I32P] * 4)
+    L.tfhe_amd_lut_fill_many.argtypes = [_I32P, ctypes.c_int, ctypes.c_int, ctypes.c_int, _I32P]
+    for f in ("tfhe_amd_bootstrap_lut_many_woks_batch_dev", "tfhe_amd_bootstrap_lut_many_batch_dev"):
+        getattr(L, f).argtypes = ([_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_int32, ctypes.c_int32, _VP, _VP, ctypes.c_int32] + [_VP] * 4 + [_VP])
+    for f in ("tfhe_amd_bootstrap_lut_many_woks_batch_host", "tfhe_amd_bootstrap_lut_many_batch_host"):
+        getattr(L, f).argtypes = ([_VP, ctypes.c_int, ctypes.c_int, _I32P, _I32P, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_int32, ctypes.c_int32, _I32P, _I32P, ctypes.c_int32] + [_I32P] * 4)
     L.tfhe_amd_blind_rotate_dev.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]
     L.tfhe_amd_external_product_dev.argtypes = [_VP, ctypes.c_int, _VP, _VP, _VP]
     L.tfhe_amd_context_create_replica.argtypes = [_VP, ctypes.c_int, ctypes.POINTER(_VP)]
@@ -221,6 +228,18 @@ def lut_table(p, values):
         raise TfheAmdError(f"values: need {p} Torus32 words, got shape {v.shape}")
     tv = np.zeros(N, np.int32)
     _check(lib.tfhe_amd_lut_fill(_p(tv), int(p), _p(v)), "lut_fill")
+    return tv
+
+
+def lut_table_many(p, values, log_nu):
+    """tfhe_amd_lut_fill_many: the test vector int32 [1024] that interleaves the n_fn <= 2^log_nu
+    functions values [n_fn][p] (Torus32 words), tv[j] = values[j mod nu][floor(j p / N)] (0 where
+    j mod nu >= n_fn), so output f of a many-LUT bootstrap at log_nu reads values[f][m]."""
+    v = np.ascontiguousarray(np.asarray(values).astype(np.int64).astype(np.int32))
+    if v.ndim != 2 or v.shape[0] < 1 or v.shape[1] != int(p):
+        raise TfheAmdError(f"values: need [n_fn][{p}] Torus32 words, got shape {v.shape}")
+    tv = np.zeros(N, np.int32)
+    _check(lib.tfhe_amd_lut_fill_many(_p(tv), int(p), int(log_nu), v.shape[0], _p(v)), "lut_fill_many")
     return tv
 
 
@@ -636,6 +655,67 @@ class Context:
         """tfhe_amd_bootstrap_lut_batch_dev on torch tensors; res may alias x"""
         self._lut_dev(True, tv, res_a, res_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream)
 
+    # ---- many-LUT bootstrapping (tfhe_amd_bootstrap_lut_many_*): as the lut_* methods, with the
+    # modulus switch to a multiple of 2^log_nu and n_out <= 2^log_nu outputs per ciphertext,
+    # function-major ([n_out][B][...])
+    def _lut_many_host(self, ks, tv, log_nu, n_out, x_a, x_b, lut_index, c, sa, sb, y_a, y_b):
+        tv = i32(tv).reshape(-1, N)
+        x_a = i32(x_a); B = x_a.shape[0]
+        idx = None if lut_index is None else i32(lut_index)
+        if idx is not None and idx.shape != (B,):
+            raise TfheAmdError(f"lut_index: need one table index per ciphertext ({B}), got {idx.shape}")
+        if int(sb) != 0 and (y_a is None or y_b is None):
+            raise TfheAmdError("sb != 0 needs y_a, y_b")
+        n = max(int(n_out), 1)
+        r_a = np.zeros((n, B, n_lwe if ks else N), np.int32); r_b = np.zeros((n, B), np.int32)
+        fn = lib.tfhe_amd_bootstrap_lut_many_batch_host if ks else lib.tfhe_amd_bootstrap_lut_many_woks_batch_host
+        _check(fn(self.h, B, tv.shape[0], _p(tv), _p(idx), int(log_nu), int(n_out), int(c), int(sa), _p(x_a),
+                  _p(i32(x_b)), int(sb), _p(None if y_a is None else i32(y_a)),
+                  _p(None if y_b is None else i32(y_b)), _p(r_a), _p(r_b)),
+               "bootstrap_lut_many_batch_host" if ks else "bootstrap_lut_many_woks_batch_host")
+        return r_a, r_b
+
+    def lut_many_woks_host(self, tv, log_nu, n_out, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None):
+        """tfhe_amd_bootstrap_lut_many_woks_batch_host -> (u_a [n_out][B][1024], u_b [n_out][B])"""
+        return self._lut_many_host(False, tv, log_nu, n_out, x_a, x_b, lut_index, c, sa, sb, y_a, y_b)
+
+    def lut_many_bootstrap_host(self, tv, log_nu, n_out, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None,
+                                y_b=None):
+        """tfhe_amd_bootstrap_lut_many_batch_host -> (r_a [n_out][B][500], r_b [n_out][B])"""
+        return self._lut_many_host(True, tv, log_nu, n_out, x_a, x_b, lut_index, c, sa, sb, y_a, y_b)
+
+    def _lut_many_dev(self, ks, tv, log_nu, n_out, out_a, out_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream):
+        B = x_a.shape[0]
+        if tv is None or tv.dim() != 2 or tv.shape[0] < 1:
+            raise TfheAmdError("tv: need a GPU tensor [n_lut][1024]")
+        n_lut = tv.shape[0]
+        n = max(int(n_out), 1)
+        named = [("tv", tv, (n_lut, N)), ("out_a", out_a, (n, B, n_lwe if ks else N)), ("out_b", out_b, (n, B)),
+                 ("x_a", x_a, (B, n_lwe)), ("x_b", x_b, (B,))]
+        if lut_index is not None:
+            named.append(("lut_index", lut_index, (B,)))
+        if int(sb) != 0:
+            named += [("y_a", y_a, (B, n_lwe)), ("y_b", y_b, (B,))]
+        for name, t, shape in named:
+            self._dev_check(t, shape, name)
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        fn = lib.tfhe_amd_bootstrap_lut_many_batch_dev if ks else lib.tfhe_amd_bootstrap_lut_many_woks_batch_dev
+        _check(fn(self.h, B, n_lut, ptr(tv), ptr(lut_index), int(log_nu), int(n_out), int(c), int(sa), ptr(x_a),
+                  ptr(x_b), int(sb), ptr(y_a) if int(sb) else None, ptr(y_b) if int(sb) else None, ptr(out_a),
+                  ptr(out_b), stream),
+               "bootstrap_lut_many_batch_dev" if ks else "bootstrap_lut_many_woks_batch_dev")
+
+    def lut_many_woks_dev(self, tv, log_nu, n_out, u_a, u_b, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None,
+                          y_b=None, stream=None):
+        """tfhe_amd_bootstrap_lut_many_woks_batch_dev on torch tensors: u_a [n_out][B][1024], u_b [n_out][B]"""
+        self._lut_many_dev(False, tv, log_nu, n_out, u_a, u_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream)
+
+    def lut_many_bootstrap_dev(self, tv, log_nu, n_out, res_a, res_b, x_a, x_b, lut_index=None, c=0, sa=1, sb=0,
+                               y_a=None, y_b=None, stream=None):
+        """tfhe_amd_bootstrap_lut_many_batch_dev on torch tensors: res_a [n_out][B][500], res_b [n_out][B];
+        res may overlap x"""
+        self._lut_many_dev(True, tv, log_nu, n_out, res_a, res_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream)
+
     def blind_rotate_dev(self, acc, bara, iters, stream=None):
         B = acc.shape[0]
         self._dev_check(acc, (B, 2, 1024), "acc")
@@ -826,6 +906,10 @@ lib.tfhe_amd_circuit_gate.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_
 lib.tfhe_amd_circuit_lincomb.argtypes = [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_int32,
                                          ctypes.c_int, ctypes.c_int32, ctypes.c_int]
 LUT_GATE = -2   # gate code tfhe_amd_circuit_node reports for a programmable-bootstrap node
+LUT_MANY_GATE = -3   # ... for every wire of a many-LUT node
+lib.tfhe_amd_circuit_lut_many.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
+                                          ctypes.c_int, ctypes.c_int32, ctypes.c_int, ctypes.c_int32, ctypes.c_int]
+lib.tfhe_amd_circuit_lut_many_node.argtypes = [_VP, ctypes.c_int, _IP, ctypes.POINTER(ctypes.c_int32), _IP, _IP, _IP]
 lib.tfhe_amd_circuit_lut_table.argtypes = [_VP, _I32P]
 lib.tfhe_amd_circuit_lut_table_get.argtypes = [_VP, ctypes.c_int, _I32P]
 lib.tfhe_amd_circuit_lut.argtypes = [_VP, ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int, ctypes.c_int32,
@@ -924,6 +1008,22 @@ class Circuit:
         t, c0 = ctypes.c_int(), ctypes.c_int32()
         _check(lib.tfhe_amd_circuit_lut_node(self.h, int(w), ctypes.byref(t), ctypes.byref(c0)), "circuit_lut_node")
         return t.value, c0.value
+
+    def lut_many(self, table, log_nu, n_out, c0, sa, a, sb=0, b=-1, sc=0, c=-1):
+        """tfhe_amd_circuit_lut_many: ONE bootstrap of (0, c0) + sa*a + sb*b + sc*c through `table`
+        with the modulus switch to a multiple of 2^log_nu; defines n_out consecutive wires (wire
+        first + f = the extraction at index f) and returns the first"""
+        return self._w(lib.tfhe_amd_circuit_lut_many(self.h, int(table), int(log_nu), int(n_out), int(c0), int(sa),
+                                                     int(a), int(sb), int(b), int(sc), int(c)), "lut_many")
+
+    def lut_many_node(self, w):
+        """(table id, c0, log_nu, n_out, index) of wire w of a many-LUT node (node(w) reports gate -3
+        and the table id as c0)"""
+        t, c0 = ctypes.c_int(), ctypes.c_int32()
+        th, n, ix = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _check(lib.tfhe_amd_circuit_lut_many_node(self.h, int(w), ctypes.byref(t), ctypes.byref(c0), ctypes.byref(th),
+                                                  ctypes.byref(n), ctypes.byref(ix)), "circuit_lut_many_node")
+        return t.value, c0.value, th.value, n.value, ix.value
 
     def _vec(self, fn, a, b, n_out, *extra):
         out = (ctypes.c_int * n_out)()
@@ -1024,6 +1124,9 @@ class Circuit:
             if gate == LUT_GATE:
                 raise TfheAmdError(f"eval_plain evaluates bits; wire {w} is a LUT node (multi-valued): evaluate it "
                                    "from its table (lut_node, lut_table_get)")
+            if gate == LUT_MANY_GATE:
+                raise TfheAmdError(f"eval_plain evaluates bits; wire {w} belongs to a many-LUT node (multi-valued): "
+                                   "evaluate it from its table (lut_many_node, lut_table_get)")
             if kind == 0:
                 val[w] = np.where(np.asarray(bits[w]) != 0, e8, -e8).astype(np.int64)
             elif kind == 2:

@@ -190,6 +190,59 @@ int tfhe_amd_bootstrap_lut_batch_host(TfheAmdContext *ctx, int B, int n_lut, con
                                       const int32_t *y_a, const int32_t *y_b,
                                       int32_t *res_a, int32_t *res_b);
 
+/* ---- Many-LUT bootstrapping: up to nu = 2^log_nu functions of one input from
+ * ONE blind rotation (PBS-manyLUT; Chillotti, Ligier, Orfila, Tap 2021).  The modulus switch
+ * rounds every mask word and the body to a multiple of nu,
+ * bar(x) = ((((uint64)x + 2^(20+log_nu)) >> (21+log_nu)) << log_nu) mod 2N, the 500 CMux steps
+ * are the ordinary ones, and the extraction takes the coefficients f = 0 .. n_out-1 of the
+ * rotated accumulator instead of only coefficient 0: output f encrypts tv[bar + f] (negacyclic),
+ * so a test vector that interleaves the functions, tv[j] = function (j mod nu) at box
+ * floor(j p / N), yields function f in output f.  The coarser switch costs margin: the phase
+ * error of the switch grows about nu-fold (DESIGN.md §3.3 has the measured figures; p nu <= 16
+ * decodes fresh inputs with room to spare).
+ *
+ * tfhe_amd_lut_fill_many: tv[j] = values[j & (nu-1)][floor(j p / N)] when (j & (nu-1)) < n_fn,
+ * else 0; values is [n_fn][p] Torus32.  TFHE_AMD_E_ARG unless p is a power of two,
+ * 0 <= log_nu <= 4, 1 <= n_fn <= nu, p nu <= 1024 and the pointers are non-null (tv is then
+ * untouched).  log_nu = 0, n_fn = 1 is tfhe_amd_lut_fill.  Host only, needs no GPU. */
+int tfhe_amd_lut_fill_many(int32_t tv[1024], int p, int log_nu, int n_fn, const int32_t *values /* [n_fn][p] */);
+
+/* The batch forms: the arguments of the tfhe_amd_bootstrap_lut_* function of the same name with
+ * log_nu, n_out after lut_index.  Outputs are function-major, u_a [n_out][B][1024], u_b [n_out][B]
+ * and res_a [n_out][B][500], res_b [n_out][B], so each function's block is an ordinary batch for
+ * the next call; the key-switched forms run one key switch over the n_out B samples, and res may
+ * alias X.  Everything said of the single-table forms holds (lut_index clamped on the device and
+ * checked on the host, guard, tfhe_amd_select_kernel, asynchronous _dev forms).  The exactness
+ * guard is per ciphertext: a flagged one is recomputed exactly with the same log_nu and table and
+ * all its n_out outputs rewritten; tfhe_amd_guard_stats counts ciphertexts.  TFHE_AMD_E_ARG
+ * additionally for log_nu outside [0, 4] or n_out outside [1, 2^log_nu].  tfhe_amd_last_kernels
+ * says "lut-many" where the single-table launches say "lut", e.g.
+ * "k_blind_rotate_v6(lut-many+reg-rotation)", "k_blind_rotate_v4(lut-many+guard)". */
+int tfhe_amd_bootstrap_lut_many_woks_batch_dev(TfheAmdContext *ctx, int B, int n_lut, const int32_t *tv,
+                                               const int32_t *lut_index, int log_nu, int n_out,
+                                               int32_t c, int32_t sa,
+                                               const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                               const int32_t *y_a, const int32_t *y_b,
+                                               int32_t *u_a, int32_t *u_b, void *stream);
+int tfhe_amd_bootstrap_lut_many_batch_dev(TfheAmdContext *ctx, int B, int n_lut, const int32_t *tv,
+                                          const int32_t *lut_index, int log_nu, int n_out,
+                                          int32_t c, int32_t sa,
+                                          const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                          const int32_t *y_a, const int32_t *y_b,
+                                          int32_t *res_a, int32_t *res_b, void *stream);
+int tfhe_amd_bootstrap_lut_many_woks_batch_host(TfheAmdContext *ctx, int B, int n_lut, const int32_t *tv,
+                                                const int32_t *lut_index, int log_nu, int n_out,
+                                                int32_t c, int32_t sa,
+                                                const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                                const int32_t *y_a, const int32_t *y_b,
+                                                int32_t *u_a, int32_t *u_b);
+int tfhe_amd_bootstrap_lut_many_batch_host(TfheAmdContext *ctx, int B, int n_lut, const int32_t *tv,
+                                           const int32_t *lut_index, int log_nu, int n_out,
+                                           int32_t c, int32_t sa,
+                                           const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                           const int32_t *y_a, const int32_t *y_b,
+                                           int32_t *res_a, int32_t *res_b);
+
 /* Debug/parity entry: run `iters` CMux steps of the blind rotation (i = 0..iters-1,
  * tfhe_MuxRotate_FFT, skipping bara_i == 0 like tfhe_blindRotate_FFT) on B explicit
  * accumulators acc [B][2][1024] in place, with rotations bara [B][iters].  The raw steps of the
@@ -396,6 +449,22 @@ int tfhe_amd_circuit_lut_table_get(const TfheAmdCircuit *c, int table, int32_t o
  * TFHE_AMD_E_ARG for any other node.  The fields of all other node kinds are as before. */
 int tfhe_amd_circuit_node(const TfheAmdCircuit *c, int w, int *kind, int *gate, int32_t *c0, int32_t *s, int *in);
 int tfhe_amd_circuit_lut_node(const TfheAmdCircuit *c, int w, int *table, int32_t *c0);
+/* Many-LUT node (the batch form: tfhe_amd_bootstrap_lut_many_*): ONE bootstrapped row that
+ * defines n_out consecutive wires, wire first + f = KS(SampleExtract_f(BlindRotate(...))) with the
+ * modulus switch to a multiple of 2^log_nu; returns the first wire id.  It is levelled like any
+ * row and may share a level, and so one blind-rotation launch, with gate rows, LUT rows and
+ * many-LUT rows of another log_nu; its outputs are n_out entries of the level's one key-switch
+ * launch.  tfhe_amd_circuit_info counts one bootstrap and one gate per node and n_out wires,
+ * tfhe_amd_circuit_level_sizes one row.  TFHE_AMD_E_ARG (nothing added) for an unknown table or
+ * wire, log_nu outside [0, 4] or n_out outside [1, 2^log_nu].
+ * tfhe_amd_circuit_node reports each of the node's wires as kind 1, gate code -3, the TABLE ID in
+ * *c0 and coefficients and inputs as a lincomb; tfhe_amd_circuit_lut_many_node returns the rest
+ * (index = the position of w within its node, the extraction index) and TFHE_AMD_E_ARG for any
+ * other node. */
+int tfhe_amd_circuit_lut_many(TfheAmdCircuit *c, int table, int log_nu, int n_out, int32_t c0, int32_t sa, int a,
+                              int32_t sb, int b, int32_t sc, int cc);
+int tfhe_amd_circuit_lut_many_node(const TfheAmdCircuit *c, int w, int *table, int32_t *c0, int *log_nu, int *n_out,
+                                   int *index);
 /* compile (if needed) and report size: wires, gates, bootstraps per instance, depth */
 int tfhe_amd_circuit_info(TfheAmdCircuit *c, int *n_wires, int *n_gates, int *n_bootstraps, int *depth);
 /* rows (bootstraps) per level, level 0 first (level 0 is bootstrap-free); returns #levels */
