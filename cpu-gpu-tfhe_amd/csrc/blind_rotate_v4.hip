@@ -255,6 +255,10 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4(V4Args g, 
         t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
         t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
         t.za = nullptr; t.zb = nullptr;
+        if constexpr (LUT) {   // the third input (engine.h BrInput): LUT and many-LUT launches only
+            t.sc = in.sc;
+            t.za = in.sc ? in.z_a + (size_t)idx * kn : nullptr; t.zb = in.sc ? in.z_b + idx : nullptr;
+        }
         if constexpr (MANY)   // one half: output f of ciphertext gct is u sample f B + gct
             br_v4_body<true, true>(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct,
                                    lut_table(in.tv, in.lut_index, in.n_lut, idx),
@@ -425,6 +429,9 @@ hipError_t launch_blind_rotate_v4(const DeviceKey &key, int B, int halves, const
     if (many && (!lut || halves != 1 || in[0].log_nu < 0 || in[0].log_nu > 4 || in[0].n_out < 1 ||
                  in[0].n_out > (1 << in[0].log_nu)))
         return hipErrorInvalidValue;
+    // third input (engine.h BrInput): only the LUT instantiations read it
+    for (const BrInput *h : {&in[0], &in1})
+        if (h->sc && (!lut || !h->z_a || !h->z_b)) return hipErrorInvalidValue;
     if (many) {
         trace_kernel(gd.flags ? "k_blind_rotate_v4(lut-many+guard)" : "k_blind_rotate_v4(lut-many)");
         if (gd.flags)

@@ -512,6 +512,10 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6(V6Args g,
     t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
     t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
     t.za = nullptr; t.zb = nullptr;
+    if constexpr (LUT) {   // the third input (engine.h BrInput): LUT and many-LUT launches only
+        t.sc = in.sc;
+        t.za = in.sc ? in.z_a + (size_t)idx * kn : nullptr; t.zb = in.sc ? in.z_b + idx : nullptr;
+    }
     if constexpr (MANY)   // one half: output f of ciphertext gct is u sample f B + gct
         br_v6_body<WAVES, RREG, 1, false, true, true>(
             sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct, true,
@@ -545,6 +549,10 @@ __global__ __launch_bounds__(2 * kV6Threads, WAVES) void k_blind_rotate_v6p(V6Ar
     t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
     t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
     t.za = nullptr; t.zb = nullptr;
+    if constexpr (LUT) {   // the third input (engine.h BrInput): LUT and many-LUT launches only
+        t.sc = in.sc;
+        t.za = in.sc ? in.z_a + (size_t)idx * kn : nullptr; t.zb = in.sc ? in.z_b + idx : nullptr;
+    }
     // (the padding ciphertext repeats the last live one, table included)
     if constexpr (MANY)
         br_v6_body<WAVES, true, 2, PS, true, true>(
@@ -824,6 +832,9 @@ hipError_t launch_blind_rotate_v6(const DeviceKey &key, int B, int halves, const
     if (many && (!lut || halves != 1 || in[0].log_nu < 0 || in[0].log_nu > 4 || in[0].n_out < 1 ||
                  in[0].n_out > (1 << in[0].log_nu)))
         return hipErrorInvalidValue;
+    // third input (engine.h BrInput): only the LUT instantiations read it
+    for (const BrInput *h : {&in[0], &in1})
+        if (h->sc && (!lut || !h->z_a || !h->z_b)) return hipErrorInvalidValue;
     for (long base = 0; base < total; base += chunk) {
         const long n = total - base < chunk ? total - base : chunk;
         if (lut) {

@@ -47,6 +47,8 @@ struct Node {
 };
 constexpr int kLutGate = -2;   // gate code of a LUT node (tfhe_amd_circuit_node)
 constexpr int kManyGate = -3;  // gate code of every wire of a many-LUT node
+constexpr int kAffineGate = -4;  // gate code of an affine node (0, c0) + s[0] W[in[0]] (kind 2)
+constexpr int32_t kH0 = 1 << 28;   // half-torus bit 0: 1/16; bit 1 is 3 kH0
 constexpr int kExtraRow = 1 << 30;   // compile: a u row behind the level's rows, until their number is known
 
 struct Affine {          // W = (0, c) + s W[base]; base = -1: the trivial sample (0, c)
@@ -93,6 +95,9 @@ struct TfheAmdCircuit {
     // programmable-bootstrap test vectors [n][kN]; uploaded behind the level tables, where the LUT
     // rows find them by a self-relative offset (engine.h CircRow.lut)
     std::vector<int32_t> luts;
+    // carry-save cells: table ids, registered at first use (-1: not yet);
+    // fa_table[2 enc_sum + enc_carry], sign_table: the constant test vector 1/16
+    int fa_table[4] = {-1, -1, -1, -1}, sign_table = -1;
     int n_boot = 0, max_rows = 0;   // max_rows: the largest level's u rows
     // per executing context (keyed by the context): device tables + scratch
     std::mutex mu;   // compile + the state map; runs on distinct contexts proceed concurrently
@@ -197,7 +202,12 @@ int compile(TfheAmdCircuit *C) {
         if (nd.kind == 2) {
             Affine a;
             if (nd.gate == TFHE_GATE_CONST) a = Affine{nd.c0, 0, -1};
-            else {
+            else if (nd.gate == kAffineGate) {
+                const Affine &x = aff[nd.in[0]];
+                const uint32_t sg = (uint32_t)nd.s[0];
+                a = Affine{(int32_t)((uint32_t)nd.c0 + sg * (uint32_t)x.c), (int32_t)(sg * (uint32_t)x.s), x.base};
+                if (a.s == 0) a.base = -1;   // s = 0 (or folded to 0 mod 2^32): the trivial sample
+            } else {
                 const Affine &x = aff[nd.in[0]];
                 const int32_t sg = nd.gate == TFHE_GATE_NOT ? -1 : 1;
                 a = Affine{(int32_t)((uint32_t)sg * (uint32_t)x.c), (int32_t)((uint32_t)sg * (uint32_t)x.s), x.base};
@@ -406,6 +416,83 @@ extern "C" int tfhe_amd_circuit_lut_many_node(const TfheAmdCircuit *c, int w, in
     return TFHE_AMD_OK;
 }
 
+// ------------------------------------------------------------------ carry-save cells
+// Half-torus bits (H): 1/16 for 0, 3/16 for 1, the p = 4 boxes 0 and 1 of tfhe_amd_lut_fill's
+// convention.  Up to three of them plus -(k - 1)/16 sum to the centre of box m = a + b (+ c) in
+// [0, 3], which fills the half torus exactly; one many-LUT row (log_nu = 1) reads the sum bit
+// m & 1 at index 0 and the carry m >> 1 at index 1.
+
+namespace {
+
+bool enc_ok(int e) { return e == TFHE_AMD_ENC_GATE || e == TFHE_AMD_ENC_HALF; }
+int32_t enc_bit(int enc, int bit) { return enc == TFHE_AMD_ENC_HALF ? (bit ? 3 * kH0 : kH0) : (bit ? kE8 : -kE8); }
+bool wire_ok(const TfheAmdCircuit *c, int w) { return w >= 0 && w < (int)c->nodes.size(); }
+
+// the constant test vector 1/16: a sign row that answers -+1/16
+int sign_table(TfheAmdCircuit *c) {
+    if (c->sign_table < 0) {
+        const std::vector<int32_t> tv(kN, kH0);
+        c->sign_table = tfhe_amd_circuit_lut_table(c, tv.data());
+    }
+    return c->sign_table;
+}
+
+}  // namespace
+
+extern "C" int tfhe_amd_full_add_table(int32_t *tv, int enc_sum, int enc_carry) {
+    if (!tv || !enc_ok(enc_sum) || !enc_ok(enc_carry)) return TFHE_AMD_E_ARG;
+    // tfhe_amd_lut_fill_many(tv, 4, 1, 2, {enc_sum(m & 1), enc_carry(m >> 1)}): coefficient j holds
+    // function j mod 2 of box m = floor(4 j / N)
+    for (int j = 0; j < kN; ++j) {
+        const int m = (j * 4) >> kLogN;
+        tv[j] = j & 1 ? enc_bit(enc_carry, m >> 1) : enc_bit(enc_sum, m & 1);
+    }
+    return TFHE_AMD_OK;
+}
+
+extern "C" int tfhe_amd_circuit_affine(TfheAmdCircuit *c, int32_t c0, int32_t s, int a) {
+    if (!c || !wire_ok(c, a)) return TFHE_AMD_E_ARG;
+    Node n{2, kAffineGate, c0, {s, 0, 0}, {a, -1, -1}};
+    return add_node(c, n);
+}
+
+// G = 2 H - 1/4
+extern "C" int tfhe_amd_circuit_to_gate(TfheAmdCircuit *c, int a) {
+    return tfhe_amd_circuit_affine(c, -kE4, 2, a);
+}
+
+// H = sign(G) / 16 + 1/8: one bootstrap
+extern "C" int tfhe_amd_circuit_to_half(TfheAmdCircuit *c, int a) {
+    if (!c || !wire_ok(c, a)) return TFHE_AMD_E_ARG;
+    const int r = tfhe_amd_circuit_lut(c, sign_table(c), 0, 1, a, 0, -1, 0, -1);
+    return r < 0 ? r : tfhe_amd_circuit_affine(c, kE8, 1, r);
+}
+
+// H = sign(-1/8 + a + b) / 16 + 1/8 for gate bits a, b: one bootstrap
+extern "C" int tfhe_amd_circuit_and_half(TfheAmdCircuit *c, int a, int b) {
+    if (!c || !wire_ok(c, a) || !wire_ok(c, b)) return TFHE_AMD_E_ARG;
+    const int r = tfhe_amd_circuit_lut(c, sign_table(c), -kE8, 1, a, 1, b, 0, -1);
+    return r < 0 ? r : tfhe_amd_circuit_affine(c, kE8, 1, r);
+}
+
+extern "C" int tfhe_amd_circuit_full_add(TfheAmdCircuit *c, int a, int b, int cin, int enc_sum, int enc_carry,
+                                         int *sum, int *carry) {
+    if (!c || !sum || !wire_ok(c, a) || !wire_ok(c, b) || (cin != -1 && !wire_ok(c, cin))) return TFHE_AMD_E_ARG;
+    if (!enc_ok(enc_sum) || !enc_ok(enc_carry)) return TFHE_AMD_E_ARG;
+    int &table = c->fa_table[2 * enc_sum + enc_carry];
+    if (table < 0) {
+        int32_t tv[kN];
+        tfhe_amd_full_add_table(tv, enc_sum, enc_carry);
+        table = tfhe_amd_circuit_lut_table(c, tv);
+    }
+    const int k = cin >= 0 ? 3 : 2;
+    const int w = tfhe_amd_circuit_lut_many(c, table, 1, carry ? 2 : 1, -(k - 1) * kH0, 1, a, 1, b, 1, cin);
+    if (w < 0) return w;
+    *sum = w;
+    if (carry) *carry = w + 1;
+    return TFHE_AMD_OK;
+}
+
 extern "C" int tfhe_amd_circuit_lut_node(const TfheAmdCircuit *c, int w, int *table, int32_t *c0) {
     if (!c || w < 0 || w >= (int)c->nodes.size() || c->nodes[w].gate != kLutGate) return TFHE_AMD_E_ARG;
     if (table) *table = c->nodes[w].table;
@@ -605,7 +692,10 @@ namespace {
 // Dadda reduction of bit columns (col[k] = wires of weight 2^k) to two rows, one level per
 // stage (full adders = XOR3 + MAJ, half adders = XOR + AND; target heights 2, 3, 4, 6, 9,
 // 13, ...), then a parallel-prefix adder: out[0 .. W) = the column sum mod 2^W.
-void reduce_columns(TfheAmdCircuit *c, std::vector<std::vector<int>> col, int *out) {
+// half: the wires of col are half-torus bits and every adder cell is ONE many-LUT
+// row (tfhe_amd_circuit_full_add) on the same schedule; the last two rows go back to gate bits
+// through the affine map before the prefix adder.
+void reduce_columns(TfheAmdCircuit *c, std::vector<std::vector<int>> col, int *out, bool half = false) {
     const int W = (int)col.size();
     size_t h0 = 0;
     for (auto &v : col) h0 = std::max(h0, v.size());
@@ -623,8 +713,14 @@ void reduce_columns(TfheAmdCircuit *c, std::vector<std::vector<int>> col, int *o
             int h = (int)v.size();
             size_t t = 0;
             while (h + cin > d) {
-                int s, co;
-                if (h + cin - d >= 2 && t + 3 <= v.size()) {
+                int s, co = -1;
+                const bool full = h + cin - d >= 2 && t + 3 <= v.size();
+                if (half) {   // the top column's carry is dropped: an n_out = 1 row
+                    tfhe_amd_circuit_full_add(c, v[t], v[t + 1], full ? v[t + 2] : -1, TFHE_AMD_ENC_HALF,
+                                              TFHE_AMD_ENC_HALF, &s, k + 1 < W ? &co : nullptr);
+                    t += full ? 3 : 2;
+                    h -= full ? 2 : 1;
+                } else if (full) {
                     full_add(c, v[t], v[t + 1], v[t + 2], &s, &co);
                     t += 3;
                     h -= 2;
@@ -646,8 +742,8 @@ void reduce_columns(TfheAmdCircuit *c, std::vector<std::vector<int>> col, int *o
     std::vector<int> x(W), y(W);
     for (int k = 0; k < W; ++k) {
         if (col[k].size() < 2 && zero < 0) zero = G(c, TFHE_GATE_CONST, 0);
-        x[k] = col[k].size() > 0 ? col[k][0] : zero;
-        y[k] = col[k].size() > 1 ? col[k][1] : zero;
+        x[k] = col[k].size() > 0 ? (half ? tfhe_amd_circuit_to_gate(c, col[k][0]) : col[k][0]) : zero;
+        y[k] = col[k].size() > 1 ? (half ? tfhe_amd_circuit_to_gate(c, col[k][1]) : col[k][1]) : zero;
     }
     tfhe_amd_circuit_add_prefix(c, W, x.data(), y.data(), out);
 }
@@ -680,6 +776,55 @@ extern "C" int tfhe_amd_circuit_dot(TfheAmdCircuit *c, int nterms, int nbits, co
                 if (i + j < out_bits) col[i + j].push_back(G(c, TFHE_GATE_AND, a[t * nbits + j], b[t * nbits + i]));
     reduce_columns(c, std::move(col), out);
     return TFHE_AMD_OK;
+}
+
+// The same multiplier and dot product with one-rotation adder cells: operands and
+// results are gate bits as above; the partial products leave their AND row as half-torus bits
+// (tfhe_amd_circuit_and_half, one bootstrap each as before), every full and half adder of the same
+// Dadda schedule is one many-LUT row instead of two gate rows, and the last two rows return to gate
+// bits for free.  Same depth, one bootstrap less per adder cell.
+extern "C" int tfhe_amd_circuit_mul_fa(TfheAmdCircuit *c, int nbits, const int *a, const int *b, int *prod) {
+    if (!c || nbits <= 0 || !a || !b || !prod) return TFHE_AMD_E_ARG;
+    for (int i = 0; i < nbits; ++i)
+        if (!wire_ok(c, a[i]) || !wire_ok(c, b[i])) return TFHE_AMD_E_ARG;
+    std::vector<std::vector<int>> col(2 * nbits);
+    for (int i = 0; i < nbits; ++i)
+        for (int j = 0; j < nbits; ++j) col[i + j].push_back(tfhe_amd_circuit_and_half(c, a[j], b[i]));
+    reduce_columns(c, std::move(col), prod, true);
+    return TFHE_AMD_OK;
+}
+
+extern "C" int tfhe_amd_circuit_dot_fa(TfheAmdCircuit *c, int nterms, int nbits, const int *a, const int *b,
+                                       int out_bits, int *out) {
+    if (!c || nterms <= 0 || nbits <= 0 || out_bits <= 0 || !a || !b || !out) return TFHE_AMD_E_ARG;
+    for (long i = 0; i < (long)nterms * nbits; ++i)
+        if (!wire_ok(c, a[i]) || !wire_ok(c, b[i])) return TFHE_AMD_E_ARG;
+    std::vector<std::vector<int>> col(out_bits);
+    for (int t = 0; t < nterms; ++t)
+        for (int i = 0; i < nbits; ++i)
+            for (int j = 0; j < nbits; ++j)
+                if (i + j < out_bits)
+                    col[i + j].push_back(tfhe_amd_circuit_and_half(c, a[t * nbits + j], b[t * nbits + i]));
+    reduce_columns(c, std::move(col), out, true);
+    return TFHE_AMD_OK;
+}
+
+// ripple add of two vectors of half-torus bits, one many-LUT row per bit (against two gate rows
+// per bit in tfhe_amd_circuit_add): the carries stay half-torus bits, the sum bits and the
+// returned carry-out are emitted in enc_out; carry_in (-1: none) is a half-torus bit
+extern "C" int tfhe_amd_circuit_add_half(TfheAmdCircuit *c, int nbits, const int *a, const int *b, int carry_in,
+                                         int enc_out, int *sum) {
+    if (!c || nbits <= 0 || !a || !b || !sum || !enc_ok(enc_out)) return TFHE_AMD_E_ARG;
+    if (carry_in != -1 && !wire_ok(c, carry_in)) return TFHE_AMD_E_ARG;
+    for (int i = 0; i < nbits; ++i)
+        if (!wire_ok(c, a[i]) || !wire_ok(c, b[i])) return TFHE_AMD_E_ARG;
+    int carry = carry_in;
+    for (int i = 0; i < nbits; ++i) {
+        const int rc = tfhe_amd_circuit_full_add(c, a[i], b[i], carry, enc_out,
+                                                 i + 1 < nbits ? TFHE_AMD_ENC_HALF : enc_out, &sum[i], &carry);
+        if (rc < 0) return rc;
+    }
+    return carry;
 }
 
 // ------------------------------------------------------------------ Cipher's remaining operators

@@ -194,6 +194,7 @@ struct TfheAmdContext {
     void *mtab = nullptr;       // mixed-gate batches: device row / key-switch tables
     size_t mtab_bytes = 0;
     int mtab_rows = 0;          // rows of the last mixed-gate batch (its key-switch table follows them)
+    int32_t *fa_tab = nullptr;  // full-adder tables [2 enc_sum + enc_carry][kN] (tfhe_amd_full_add_batch_*), made at first use
 };
 
 // Collects the launches of one C-ABI batch call into its context's last_kernels; nested calls
@@ -385,10 +386,25 @@ extern "C" int tfhe_amd_context_destroy(TfheAmdContext *c) {
     if (c->h_vout) (void)hipHostFree(c->h_vout);
     if (c->d_vout) (void)hipFree(c->d_vout);
     free_scratch(c);
+    if (c->fa_tab) (void)hipFree(c->fa_tab);
     if (c->gstats) (void)hipFree(c->gstats);
     if (!c->shared_key) free_key(c->key);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
+    return TFHE_AMD_OK;
+}
+
+// The four full-adder tables (tfhe_amd_full_add_table) on the context's device: 16 KB, made at the
+// first tfhe_amd_full_add_batch_* call (or with a replica of a context that has them) and freed
+// with the context.  Not key material: key_buffers below does not list them.
+static int full_add_tables(TfheAmdContext *c) {
+    if (c->fa_tab) return TFHE_AMD_OK;
+    std::vector<int32_t> h((size_t)4 * kN);
+    for (int e = 0; e < 4; ++e) tfhe_amd_full_add_table(h.data() + (size_t)e * kN, e >> 1, e & 1);
+    DeviceScope dev_scope(c->device);
+    HIPCHK(dev_scope.rc);
+    HIPCHK(hipMalloc(&c->fa_tab, sizeof(int32_t) * h.size()));
+    HIPCHK(hipMemcpy(c->fa_tab, h.data(), sizeof(int32_t) * h.size(), hipMemcpyHostToDevice));
     return TFHE_AMD_OK;
 }
 
@@ -461,6 +477,7 @@ extern "C" int tfhe_amd_context_create_replica(TfheAmdContext *src, int device, 
     if (hipStreamSynchronize(c->stream) != hipSuccess) return fail(TFHE_AMD_E_HIP);
     const int rc = tfhe_amd_reserve(c, 64);
     if (rc != TFHE_AMD_OK) return fail(rc);
+    if (src->fa_tab && full_add_tables(c) != TFHE_AMD_OK) return fail(TFHE_AMD_E_HIP);   // a replica of a context that has them
     *out = c;
     return TFHE_AMD_OK;
 }
@@ -730,13 +747,14 @@ static bool many_args_ok(int log_nu, int n_out) {
 static int lut_batch_dev(TfheAmdContext *c, bool ks, int B, int n_lut, const int32_t *tv, const int32_t *lut_index,
                          int32_t cst, int32_t sa, const int32_t *x_a, const int32_t *x_b, int32_t sb,
                          const int32_t *y_a, const int32_t *y_b, int32_t *out_a, int32_t *out_b, void *stream,
-                         int log_nu = 0, int n_out = 0) {
+                         int log_nu = 0, int n_out = 0, int32_t sc = 0, const int32_t *z_a = nullptr,
+                         const int32_t *z_b = nullptr) {
     if (!c || B < 0 || n_lut <= 0 || !tv || !c->key.has_bk || (ks && !c->key.ksk)) return TFHE_AMD_E_ARG;
     if (n_out != 0 && !many_args_ok(log_nu, n_out)) return TFHE_AMD_E_ARG;
     const int n_res = n_out ? n_out : 1;
     if ((long)B * n_res > 0x3fffffffL) return TFHE_AMD_E_ARG;
     if (B == 0) return TFHE_AMD_OK;
-    if (!x_a || !x_b || !out_a || !out_b || (sb && (!y_a || !y_b))) return TFHE_AMD_E_ARG;
+    if (!x_a || !x_b || !out_a || !out_b || (sb && (!y_a || !y_b)) || (sc && (!z_a || !z_b))) return TFHE_AMD_E_ARG;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     DeviceScope dev_scope(c->device);
@@ -746,7 +764,8 @@ static int lut_batch_dev(TfheAmdContext *c, bool ks, int B, int n_lut, const int
     int rc = tfhe_amd_reserve(c, B * n_res);
     if (rc) return rc;
     HIPCHK(c->fence.acquire(s));
-    BrInput in{x_a, x_b, sb ? y_a : nullptr, sb ? y_b : nullptr, cst, sa, sb, n_lut, tv, lut_index, log_nu, n_out};
+    BrInput in{x_a, x_b, sb ? y_a : nullptr, sb ? y_b : nullptr, cst, sa, sb, n_lut, tv, lut_index, log_nu, n_out,
+               sc ? z_a : nullptr, sc ? z_b : nullptr, sc};
     {
         ProfScope ps(c, s, true);
         const Guard gd = ctx_guard(c);
@@ -778,6 +797,31 @@ extern "C" int tfhe_amd_bootstrap_lut_many_batch_dev(TfheAmdContext *c, int B, i
     if (!many_args_ok(log_nu, n_out)) return TFHE_AMD_E_ARG;
     return lut_batch_dev(c, true, B, n_lut, tv, lut_index, cst, sa, x_a, x_b, sb, y_a, y_b, res_a, res_b, stream,
                          log_nu, n_out);
+}
+
+// One-rotation full adders: B cells on half-torus bits, (0, -(k - 1)/16) + a + b
+// (+ c) through the context's table for (enc_sum, enc_carry): one many-LUT launch (log_nu = 1,
+// n_out = 2) and one key switch over the 2 B samples
+static bool enc_ok(int e) { return e == TFHE_AMD_ENC_GATE || e == TFHE_AMD_ENC_HALF; }
+static bool full_add_args_ok(TfheAmdContext *c, int B, int enc_sum, int enc_carry, const int32_t *c_a,
+                             const int32_t *c_b) {
+    return c && B >= 0 && enc_ok(enc_sum) && enc_ok(enc_carry) && (c_a != nullptr) == (c_b != nullptr);
+}
+
+extern "C" int tfhe_amd_full_add_batch_dev(TfheAmdContext *c, int B, int enc_sum, int enc_carry, const int32_t *a_a,
+                                           const int32_t *a_b, const int32_t *b_a, const int32_t *b_b,
+                                           const int32_t *c_a, const int32_t *c_b, int32_t *res_a, int32_t *res_b,
+                                           void *stream) {
+    if (!full_add_args_ok(c, B, enc_sum, enc_carry, c_a, c_b) || !c->key.has_bk || !c->key.ksk) return TFHE_AMD_E_ARG;
+    if (B == 0) return TFHE_AMD_OK;
+    if (!a_a || !a_b || !b_a || !b_b || !res_a || !res_b) return TFHE_AMD_E_ARG;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    const int rc = full_add_tables(c);
+    if (rc) return rc;
+    const int k = c_a ? 3 : 2;
+    return lut_batch_dev(c, true, B, 1, c->fa_tab + (size_t)(2 * enc_sum + enc_carry) * kN, nullptr,
+                         -(k - 1) * (1 << 28), 1, a_a, a_b, 1, b_a, b_b, res_a, res_b, stream, 1, 2, c_a ? 1 : 0, c_a,
+                         c_b);
 }
 
 extern "C" int tfhe_amd_bootstrap_lut_woks_batch_dev(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,
@@ -1610,6 +1654,40 @@ static int lut_batch_host(TfheAmdContext *c, bool ks, int B, int n_lut, const in
     HIPCHK(hipStreamSynchronize(c->stream));
     memcpy(out_a, h + o_out, Ao * 4);
     memcpy(out_b, h + o_out + Ao, Bo * 4);
+    return TFHE_AMD_OK;
+}
+
+// the staged path: [a | b | c | res] in the io scratch (5 B x 501 words; res may alias an input)
+extern "C" int tfhe_amd_full_add_batch_host(TfheAmdContext *c, int B, int enc_sum, int enc_carry, const int32_t *a_a,
+                                            const int32_t *a_b, const int32_t *b_a, const int32_t *b_b,
+                                            const int32_t *c_a, const int32_t *c_b, int32_t *res_a, int32_t *res_b) {
+    if (!full_add_args_ok(c, B, enc_sum, enc_carry, c_a, c_b)) return TFHE_AMD_E_ARG;
+    if (B == 0) return TFHE_AMD_OK;
+    if (!a_a || !a_b || !b_a || !b_b || !res_a || !res_b) return TFHE_AMD_E_ARG;
+    const size_t Ai = (size_t)B * kn, In = Ai + B, n_in = c_a ? 3 : 2, o_out = n_in * In;
+    const size_t need = o_out + 2 * In, cap = (need + io_words(1) - 1) / io_words(1);
+    if (cap > ((size_t)1 << 24)) return TFHE_AMD_E_ARG;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceScope dev_scope(c->device);
+    HIPCHK(dev_scope.rc);
+    TraceScope trace(c);
+    int rc = tfhe_amd_reserve(c, std::max(2 * B, (int)cap));   // 2 B: the device form's extracted samples
+    if (rc) return rc;
+    int32_t *h = c->h_io, *d = c->io;
+    const int32_t *src[3][2] = {{a_a, a_b}, {b_a, b_b}, {c_a, c_b}};
+    for (size_t t = 0; t < n_in; ++t) {
+        memcpy(h + t * In, src[t][0], Ai * 4);
+        memcpy(h + t * In + Ai, src[t][1], (size_t)B * 4);
+    }
+    HIPCHK(hipMemcpyAsync(d, h, o_out * 4, hipMemcpyHostToDevice, c->stream));
+    int32_t *oa = d + o_out, *ob = oa + 2 * Ai;
+    rc = tfhe_amd_full_add_batch_dev(c, B, enc_sum, enc_carry, d, d + Ai, d + In, d + In + Ai, c_a ? d + 2 * In : nullptr,
+                                     c_a ? d + 2 * In + Ai : nullptr, oa, ob, c->stream);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(h + o_out, oa, 2 * In * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memcpy(res_a, h + o_out, 2 * Ai * 4);
+    memcpy(res_b, h + o_out + 2 * Ai, (size_t)2 * B * 4);
     return TFHE_AMD_OK;
 }
 

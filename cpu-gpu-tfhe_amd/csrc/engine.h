@@ -39,6 +39,7 @@ constexpr int kTw6Words = 4 + 4 * 4 * 64 + 8 * 64 + 2 * 64;   // fft_wave.h tabl
 // half only).  The prologue switches to a multiple of nu = 2^log_nu and the epilogue extracts the
 // coefficients f = 0 .. n_out - 1 of the rotated accumulator; output f of ciphertext g goes to u
 // sample f B + g, so u holds n_out B samples.  n_out = 0: the single-table launch above.
+// With tv set the input may have a third term: x = (0, c) + sa * X + sb * Y + sc * Z.
 struct BrInput {
     const int32_t *x_a, *x_b;
     const int32_t *y_a, *y_b;
@@ -47,6 +48,10 @@ struct BrInput {
     const int32_t *tv = nullptr;
     const int32_t *lut_index = nullptr;
     int32_t log_nu = 0, n_out = 0;
+    // third input: x += sc * Z.  Only the LUT and many-LUT instantiations read
+    // it (sc != 0 needs tv and z_a, z_b); the constant kernels keep two inputs.
+    const int32_t *z_a = nullptr, *z_b = nullptr;
+    int32_t sc = 0;
 };
 
 // One bootstrapped row of a circuit level (circuit.cpp): the blind rotation input is

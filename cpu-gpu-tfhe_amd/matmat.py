@@ -26,12 +26,13 @@ def out_bits(k, nbits, double_precision=False):
     return 2 * nbits + int(np.ceil(np.log2(max(k, 2)))) if double_precision else nbits
 
 
-def build(T, k, nbits, double_precision=False):
-    """circuit for one output element: (circuit, a wires [k][nbits], b wires [k][nbits], c wires)"""
+def build(T, k, nbits, double_precision=False, fa=False):
+    """circuit for one output element: (circuit, a wires [k][nbits], b wires [k][nbits], c wires);
+    fa: built with `Circuit.dot_fa`, one blind rotation per adder cell instead of two"""
     C = T.Circuit()
     a = [C.inputs(nbits) for _ in range(k)]
     b = [C.inputs(nbits) for _ in range(k)]
-    c = C.dot(a, b, out_bits(k, nbits, double_precision))
+    c = (C.dot_fa if fa else C.dot)(a, b, out_bits(k, nbits, double_precision))
     return C, a, b, c
 
 

@@ -26,12 +26,13 @@ def out_bits(cols, nbits):
     return 2 * nbits + int(np.ceil(np.log2(max(cols, 2))))
 
 
-def build(T, cols, nbits):
-    """circuit for one output element: (circuit, a wires [cols][nbits], x wires, y wires)"""
+def build(T, cols, nbits, fa=False):
+    """circuit for one output element: (circuit, a wires [cols][nbits], x wires, y wires); fa: built
+    with `Circuit.dot_fa`, one blind rotation per adder cell instead of two"""
     C = T.Circuit()
     a = [C.inputs(nbits) for _ in range(cols)]
     x = [C.inputs(nbits) for _ in range(cols)]
-    y = C.dot(a, x, out_bits(cols, nbits))
+    y = (C.dot_fa if fa else C.dot)(a, x, out_bits(cols, nbits))
     return C, a, x, y
 
 

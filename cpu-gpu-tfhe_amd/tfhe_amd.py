@@ -87,6 +87,9 @@ def _load():
     for f in ("tfhe_amd_bootstrap_lut_many_woks_batch_host", "tfhe_amd_bootstrap_lut_many_batch_host"):
         getattr(L, f).argtypes = ([_VP, ctypes.c_int, ctypes.c_int, _I32P, _I32P, ctypes.c_int, ctypes.c_int,
                                    ctypes.c_int32, ctypes.c_int32, _I32P, _I32P, ctypes.c_int32] + [_I32P] * 4)
+    L.tfhe_amd_full_add_table.argtypes = [_I32P, ctypes.c_int, ctypes.c_int]
+    L.tfhe_amd_full_add_batch_dev.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_VP] * 8 + [_VP]
+    L.tfhe_amd_full_add_batch_host.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int] + [_I32P] * 8
     L.tfhe_amd_blind_rotate_dev.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]
     L.tfhe_amd_external_product_dev.argtypes = [_VP, ctypes.c_int, _VP, _VP, _VP]
     L.tfhe_amd_context_create_replica.argtypes = [_VP, ctypes.c_int, ctypes.POINTER(_VP)]
@@ -240,6 +243,34 @@ def lut_table_many(p, values, log_nu):
         raise TfheAmdError(f"values: need [n_fn][{p}] Torus32 words, got shape {v.shape}")
     tv = np.zeros(N, np.int32)
     _check(lib.tfhe_amd_lut_fill_many(_p(tv), int(p), int(log_nu), v.shape[0], _p(v)), "lut_fill_many")
+    return tv
+
+
+# ---- one-rotation adder cells (include/tfhe_amd.h): the two encodings of a bit
+ENC_GATE, ENC_HALF = 0, 1
+H0, H1 = 1 << 28, 3 << 28   # half-torus bit 0 / 1: 1/16, 3/16 = lut_encode(m, 4)
+
+
+def _enc(enc):
+    return {"G": ENC_GATE, "H": ENC_HALF}.get(enc, enc) if isinstance(enc, str) else int(enc)
+
+
+def half_encode(bits):
+    """Torus32 of bits in the half-torus encoding: 1/16 for 0, 3/16 for 1"""
+    return np.where(np.asarray(bits) != 0, H1, H0).astype(np.int32)
+
+
+def half_decode(phase):
+    """the bit of a half-torus phase: box 0 or 1 of lut_decode(phase, 4); anything else means the
+    phase left the two boxes"""
+    return lut_decode(phase, 4)
+
+
+def full_add_table(enc_sum, enc_carry):
+    """tfhe_amd_full_add_table: the adder cell's test vector int32 [1024] for outputs in
+    (enc_sum, enc_carry)"""
+    tv = np.zeros(N, np.int32)
+    _check(lib.tfhe_amd_full_add_table(_p(tv), _enc(enc_sum), _enc(enc_carry)), "full_add_table")
     return tv
 
 
@@ -716,6 +747,32 @@ class Context:
         res may overlap x"""
         self._lut_many_dev(True, tv, log_nu, n_out, res_a, res_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream)
 
+    # ---- one-rotation full adders (tfhe_amd_full_add_batch_*): a, b, c = (a [B][500], b [B]) of
+    # half-torus bits, c = None: half adders; results [2][B][...]: the sum bits, then the carries
+    def full_add_host(self, enc_sum, enc_carry, a, b, c=None):
+        """tfhe_amd_full_add_batch_host -> (r_a [2][B][500], r_b [2][B])"""
+        a_a = i32(a[0]); B = a_a.shape[0]
+        r_a = np.zeros((2, B, n_lwe), np.int32); r_b = np.zeros((2, B), np.int32)
+        _check(lib.tfhe_amd_full_add_batch_host(self.h, B, _enc(enc_sum), _enc(enc_carry), _p(a_a), _p(i32(a[1])),
+                                                _p(i32(b[0])), _p(i32(b[1])), _p(None if c is None else i32(c[0])),
+                                                _p(None if c is None else i32(c[1])), _p(r_a), _p(r_b)),
+               "full_add_batch_host")
+        return r_a, r_b
+
+    def full_add_dev(self, enc_sum, enc_carry, res_a, res_b, a, b, c=None, stream=None):
+        """tfhe_amd_full_add_batch_dev on torch tensors: res_a [2][B][500], res_b [2][B]; a, b, c are
+        pairs (a [B][500], b [B]); res may overlap an input"""
+        B = a[0].shape[0]
+        named = [("res_a", res_a, (2, B, n_lwe)), ("res_b", res_b, (2, B))]
+        for nm, v in (("a", a), ("b", b)) + ((("c", c),) if c is not None else ()):
+            named += [(nm + "_a", v[0], (B, n_lwe)), (nm + "_b", v[1], (B,))]
+        for name, t, shape in named:
+            self._dev_check(t, shape, name)
+        cp = (None, None) if c is None else (c[0].data_ptr(), c[1].data_ptr())
+        _check(lib.tfhe_amd_full_add_batch_dev(self.h, B, _enc(enc_sum), _enc(enc_carry), a[0].data_ptr(),
+                                               a[1].data_ptr(), b[0].data_ptr(), b[1].data_ptr(), cp[0], cp[1],
+                                               res_a.data_ptr(), res_b.data_ptr(), stream), "full_add_batch_dev")
+
     def blind_rotate_dev(self, acc, bara, iters, stream=None):
         B = acc.shape[0]
         self._dev_check(acc, (B, 2, 1024), "acc")
@@ -907,6 +964,16 @@ lib.tfhe_amd_circuit_lincomb.argtypes = [_VP, ctypes.c_int32, ctypes.c_int32, ct
                                          ctypes.c_int, ctypes.c_int32, ctypes.c_int]
 LUT_GATE = -2   # gate code tfhe_amd_circuit_node reports for a programmable-bootstrap node
 LUT_MANY_GATE = -3   # ... for every wire of a many-LUT node
+AFFINE_GATE = -4   # ... for an affine node (kind 2): (0, c0) + s[0] * W[in[0]]
+lib.tfhe_amd_circuit_affine.argtypes = [_VP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int]
+lib.tfhe_amd_circuit_to_gate.argtypes = [_VP, ctypes.c_int]
+lib.tfhe_amd_circuit_to_half.argtypes = [_VP, ctypes.c_int]
+lib.tfhe_amd_circuit_and_half.argtypes = [_VP, ctypes.c_int, ctypes.c_int]
+lib.tfhe_amd_circuit_full_add.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          _IP, _IP]
+lib.tfhe_amd_circuit_mul_fa.argtypes = [_VP, ctypes.c_int, _IP, _IP, _IP]
+lib.tfhe_amd_circuit_dot_fa.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _IP, _IP, ctypes.c_int, _IP]
+lib.tfhe_amd_circuit_add_half.argtypes = [_VP, ctypes.c_int, _IP, _IP, ctypes.c_int, ctypes.c_int, _IP]
 lib.tfhe_amd_circuit_lut_many.argtypes = [_VP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_int32,
                                           ctypes.c_int, ctypes.c_int32, ctypes.c_int, ctypes.c_int32, ctypes.c_int]
 lib.tfhe_amd_circuit_lut_many_node.argtypes = [_VP, ctypes.c_int, _IP, ctypes.POINTER(ctypes.c_int32), _IP, _IP, _IP]
@@ -1025,6 +1092,50 @@ class Circuit:
                                                   ctypes.byref(n), ctypes.byref(ix)), "circuit_lut_many_node")
         return t.value, c0.value, th.value, n.value, ix.value
 
+    # ---- one-rotation adder cells (include/tfhe_amd.h): G = gate bits (+-1/8),
+    # H = half-torus bits (1/16, 3/16).  The library cannot check which one a wire carries.
+    def affine(self, c0, s, a):
+        """tfhe_amd_circuit_affine: the bootstrap-free wire (0, c0) + s * a"""
+        return self._w(lib.tfhe_amd_circuit_affine(self.h, int(c0), int(s), int(a)), "affine")
+
+    def to_gate(self, a):
+        """H -> G, no bootstrap"""
+        return self._w(lib.tfhe_amd_circuit_to_gate(self.h, int(a)), "to_gate")
+
+    def to_half(self, a):
+        """G -> H, one bootstrap"""
+        return self._w(lib.tfhe_amd_circuit_to_half(self.h, int(a)), "to_half")
+
+    def and_half(self, a, b):
+        """the AND of two G bits as an H bit, one bootstrap"""
+        return self._w(lib.tfhe_amd_circuit_and_half(self.h, int(a), int(b)), "and_half")
+
+    def full_add(self, a, b, cin=-1, enc_sum=ENC_HALF, enc_carry=ENC_HALF, carry=True):
+        """tfhe_amd_circuit_full_add on H wires (cin = -1: half adder): ONE bootstrap ->
+        (sum wire, carry wire); carry=False: an n_out = 1 row -> (sum wire, None)"""
+        s, co = ctypes.c_int(-1), ctypes.c_int(-1)
+        self._w(lib.tfhe_amd_circuit_full_add(self.h, int(a), int(b), int(cin), _enc(enc_sum), _enc(enc_carry),
+                                              ctypes.byref(s), ctypes.byref(co) if carry else None), "full_add")
+        return s.value, (co.value if carry else None)
+
+    def mul_fa(self, a, b):
+        """tfhe_amd_circuit_mul_fa: mul with one-rotation adder cells (G in, G out)"""
+        return self._vec("mul_fa", a, b, 2 * len(a))[0]
+
+    def dot_fa(self, a_terms, b_terms, out_bits):
+        """tfhe_amd_circuit_dot_fa: dot with one-rotation adder cells (G in, G out)"""
+        nt, nb = len(a_terms), len(a_terms[0])
+        fa = [w for v in a_terms for w in v]
+        fb = [w for v in b_terms for w in v]
+        out = (ctypes.c_int * out_bits)()
+        self._w(lib.tfhe_amd_circuit_dot_fa(self.h, nt, nb, _ids(fa), _ids(fb), int(out_bits), out), "dot_fa")
+        return list(out)
+
+    def add_half(self, a, b, carry_in=-1, enc_out=ENC_HALF):
+        """tfhe_amd_circuit_add_half: ripple add of H vectors, one row per bit -> (sum wires in
+        enc_out, carry-out wire in enc_out)"""
+        return self._vec("add_half", a, b, len(a), int(carry_in), _enc(enc_out))
+
     def _vec(self, fn, a, b, n_out, *extra):
         out = (ctypes.c_int * n_out)()
         rc = getattr(lib, "tfhe_amd_circuit_" + fn)(self.h, len(a), _ids(a), _ids(b), *extra, out)
@@ -1132,6 +1243,8 @@ class Circuit:
             elif kind == 2:
                 if gate == GATES["CONST"]:
                     val[w] = np.int64(c0)
+                elif gate == AFFINE_GATE:
+                    val[w] = np.int64(c0) + np.int64(s[0]) * enc(ins[0])
                 else:
                     val[w] = (-1 if gate == GATES["NOT"] else 1) * enc(ins[0])
             elif gate == GATES["MUX"]:

@@ -243,6 +243,28 @@ int tfhe_amd_bootstrap_lut_many_batch_host(TfheAmdContext *ctx, int B, int n_lut
                                            const int32_t *y_a, const int32_t *y_b,
                                            int32_t *res_a, int32_t *res_b);
 
+/* One-rotation full adders in a batch (the encodings, the cell and the circuit
+ * builders: below, at tfhe_amd_circuit_full_add).  B independent cells: a, b and c hold one
+ * half-torus bit (TFHE_AMD_ENC_HALF) per cell, c_a = c_b = NULL makes half adders.  One many-LUT
+ * launch over the three inputs, (0, -(k - 1)/16) + a + b (+ c) with k the number of inputs, and
+ * one key switch over the 2 B samples; results are function-major like
+ * tfhe_amd_bootstrap_lut_many_batch_*: res_a [2][B][500], res_b [2][B], block 0 the sum bits in
+ * enc_sum, block 1 the carries in enc_carry.  res may alias an input.  The entry for callers who
+ * schedule their own levels (a vector adder: one call per bit position).  The context keeps the
+ * four tables on its device (16 KB, made at the first call, freed with the context; not key
+ * material: tfhe_amd_context_key_digest / _key_bytes do not see them).  The _dev form is
+ * asynchronous on `stream`; the _host form stages through the context's buffers and is
+ * synchronous.  Guard, tfhe_amd_select_kernel and tfhe_amd_last_kernels as for the many-LUT
+ * forms ("lut-many" launches).  TFHE_AMD_E_ARG for an unknown encoding, B < 0, a null a, b or res
+ * and for exactly one of c_a, c_b null.  The library cannot check that the inputs are H bits. */
+int tfhe_amd_full_add_batch_dev(TfheAmdContext *ctx, int B, int enc_sum, int enc_carry,
+                                const int32_t *a_a, const int32_t *a_b, const int32_t *b_a, const int32_t *b_b,
+                                const int32_t *c_a, const int32_t *c_b, int32_t *res_a, int32_t *res_b,
+                                void *stream);
+int tfhe_amd_full_add_batch_host(TfheAmdContext *ctx, int B, int enc_sum, int enc_carry,
+                                 const int32_t *a_a, const int32_t *a_b, const int32_t *b_a, const int32_t *b_b,
+                                 const int32_t *c_a, const int32_t *c_b, int32_t *res_a, int32_t *res_b);
+
 /* Debug/parity entry: run `iters` CMux steps of the blind rotation (i = 0..iters-1,
  * tfhe_MuxRotate_FFT, skipping bara_i == 0 like tfhe_blindRotate_FFT) on B explicit
  * accumulators acc [B][2][1024] in place, with rotations bara [B][iters].  The raw steps of the
@@ -465,6 +487,64 @@ int tfhe_amd_circuit_lut_many(TfheAmdCircuit *c, int table, int log_nu, int n_ou
                               int32_t sb, int b, int32_t sc, int cc);
 int tfhe_amd_circuit_lut_many_node(const TfheAmdCircuit *c, int w, int *table, int32_t *c0, int *log_nu, int *n_out,
                                    int *index);
+/* ---- One-rotation adder cells.  Two encodings of a bit:
+ *   TFHE_AMD_ENC_GATE (G): -1/8 for 0, +1/8 for 1: what every gate and every builder above reads
+ *     and writes;
+ *   TFHE_AMD_ENC_HALF (H): 1/16 for 0, 3/16 for 1, the boxes 0 and 1 of tfhe_amd_lut_fill's
+ *     convention at p = 4.
+ * Two or three H bits plus -(k - 1)/16 sum to the centre of box m = a + b (+ cin) in [0, 3], which
+ * fills the half torus exactly, so ONE many-LUT row (p = 4, log_nu = 1, n_out = 2) returns the sum
+ * bit m & 1 (index 0) and the carry m >> 1 (index 1), where a full adder of gate rows takes XOR3
+ * and MAJ, two blind rotations.  Each of the two outputs is emitted in H or in G independently:
+ * four tables, tfhe_amd_full_add_table(tv, enc_sum, enc_carry) =
+ * tfhe_amd_lut_fill_many(tv, 4, 1, 2, {enc_sum(m & 1), enc_carry(m >> 1)}); host only, needs no
+ * GPU, TFHE_AMD_E_ARG for an unknown encoding or a null tv.  The cell decodes while the summed
+ * phase error of its inputs stays below 1/16 (measured 7 sigma with three
+ * bootstrapped inputs; the gate rows have 15).  Digits wider than one bit do NOT survive
+ * bootstrapped inputs on this parameter set (ibid.), so there are no radix-4 builders.
+ *
+ * THE LIBRARY CANNOT CHECK AN ENCODING: a wire is a ciphertext.  Handing a G wire to an entry that
+ * reads H (full_add, add_half, to_gate) or an H wire to one that reads G (every gate, every other
+ * builder, to_half, and_half) gives a wrong result, not an error.
+ *
+ * tfhe_amd_circuit_affine: the bootstrap-free node W = (0, c0) + s * W[a] for any c0 and s.  Like
+ * NOT / COPY / CONST it is folded into the rows that read it and also written to its own wire;
+ * tfhe_amd_circuit_node reports kind 2, gate code -4, c0, s in coefficients[0] and a in inputs[0].
+ * The noise of W[a] is multiplied by |s|.
+ * tfhe_amd_circuit_to_gate: H -> G, the affine node 2 H - 1/4 (no bootstrap; the noise doubles).
+ * tfhe_amd_circuit_to_half: G -> H, one bootstrap: a sign row through the constant test vector
+ *   1/16, then the affine node + 1/8; returns the affine node's wire (two wires are added).
+ * tfhe_amd_circuit_and_half: the AND of two G bits as an H bit, one bootstrap: the sign row
+ *   -1/8 + a + b through the constant test vector 1/16, then + 1/8 (two wires are added).
+ * tfhe_amd_circuit_full_add: one many-LUT node on the H wires a, b and cin (cin = -1: a half
+ *   adder); *sum and *carry receive the wires, emitted in enc_sum and enc_carry.  carry = NULL
+ *   makes an n_out = 1 row (a carry that is dropped).  The tables are registered with the circuit
+ *   at first use and shared by all its cells: a circuit holds at most four of them and the one
+ *   constant test vector.  Returns 0, or TFHE_AMD_E_ARG with nothing added for an unknown wire or
+ *   encoding (both encodings are checked even when carry is NULL) or a null sum.
+ * All return the new wire (affine, to_gate, to_half, and_half) or a negative TFHE_AMD_E* code. */
+enum { TFHE_AMD_ENC_GATE = 0, TFHE_AMD_ENC_HALF = 1 };
+int tfhe_amd_full_add_table(int32_t tv[1024], int enc_sum, int enc_carry);
+int tfhe_amd_circuit_affine(TfheAmdCircuit *c, int32_t c0, int32_t s, int a);
+int tfhe_amd_circuit_to_gate(TfheAmdCircuit *c, int a);
+int tfhe_amd_circuit_to_half(TfheAmdCircuit *c, int a);
+int tfhe_amd_circuit_and_half(TfheAmdCircuit *c, int a, int b);
+int tfhe_amd_circuit_full_add(TfheAmdCircuit *c, int a, int b, int cin, int enc_sum, int enc_carry, int *sum,
+                              int *carry);
+/* The builders on these cells.  mul_fa / dot_fa take and return G bits and the arguments of
+ * tfhe_amd_circuit_mul / _dot: the partial products leave their AND row as H bits (and_half, one
+ * bootstrap each as before), every full and half adder of the same Dadda schedule is one full_add
+ * row, and the last two rows go through to_gate into tfhe_amd_circuit_add_prefix (missing bits
+ * stay the G constant 0).  Same depth as mul / dot, one bootstrap less per adder cell.
+ * add_half: ripple add of two vectors of H bits (carry_in an H bit or -1), one row per bit where
+ * tfhe_amd_circuit_add has two; the sum bits and the returned carry-out wire are emitted in
+ * enc_out, so a chain of additions can stay in H.  TFHE_AMD_E_ARG for an unknown wire or encoding,
+ * nbits <= 0 or a null array. */
+int tfhe_amd_circuit_mul_fa(TfheAmdCircuit *c, int nbits, const int *a, const int *b, int *prod);
+int tfhe_amd_circuit_dot_fa(TfheAmdCircuit *c, int nterms, int nbits, const int *a, const int *b, int out_bits,
+                            int *out);
+int tfhe_amd_circuit_add_half(TfheAmdCircuit *c, int nbits, const int *a, const int *b, int carry_in, int enc_out,
+                              int *sum);
 /* compile (if needed) and report size: wires, gates, bootstraps per instance, depth */
 int tfhe_amd_circuit_info(TfheAmdCircuit *c, int *n_wires, int *n_gates, int *n_bootstraps, int *depth);
 /* rows (bootstraps) per level, level 0 first (level 0 is bootstrap-free); returns #levels */
