@@ -12,8 +12,7 @@
 //  * the accumulator is kept as a periodic negacyclic extension E[k] = +-acc[k mod N]
 //    (k < 3N, sign - when k mod 2N >= N): X^a * ACC at coefficient j is E[(j - a) mod 2N + ...]
 //    read with immediate offsets, so the rotation costs no address or sign arithmetic.
-#include "engine.h"
-#include "modarith.h"
+#include "br_common.h"
 #include "ntt_wave.h"
 
 namespace tfhe_amd {
@@ -148,13 +147,6 @@ __device__ __forceinline__ void cmux_v4(V4Shared &sh, const V4Args &g, int i, in
     __syncthreads();
 }
 
-// The linear combination x = (0, c) + sa X + sb Y + sc Z that feeds one blind rotation
-// (gate prologues boot-gates.cu:98-448; a circuit row adds a third input for MAJ / XOR3).
-struct RowTerms {
-    int32_t c, sa, sb, sc;
-    const int32_t *xa, *xb, *ya, *yb, *za, *zb;   // a rows (kn) and b words; y/z may be null
-};
-
 // prologue + modswitch + 500 CMux steps + extraction of one ciphertext into (ua, *ub).
 // LUT (programmable bootstrap, compile-time): the accumulator starts from the test vector tv [kN]
 // in device memory; tv = null (a constant row beside LUT rows) keeps the constant (mu, ..., mu)
@@ -168,19 +160,7 @@ __device__ __forceinline__ void br_v4_body(V4Shared &sh, const V4Args &g, const 
     const int tid = threadIdx.x;
     const int s = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = tid & 63;
-    // gate prologue + modulus switching (lwe-bootstrapping-functions-fft.cu:1851-1858)
-    for (int i = tid; i < kn; i += kV4Threads) {
-        uint32_t x = t.xa ? (uint32_t)t.sa * (uint32_t)t.xa[i] : 0u;
-        if (t.ya) x += (uint32_t)t.sb * (uint32_t)t.ya[i];
-        if (t.za) x += (uint32_t)t.sc * (uint32_t)t.za[i];
-        sh.bara[i] = MANY ? modswitch_nu(x, mo.th) : modswitch_2N(x);
-    }
-    if (tid == 0) {
-        uint32_t xb = (uint32_t)t.c + (t.xb ? (uint32_t)t.sa * (uint32_t)t.xb[0] : 0u);
-        if (t.yb) xb += (uint32_t)t.sb * (uint32_t)t.yb[0];
-        if (t.zb) xb += (uint32_t)t.sc * (uint32_t)t.zb[0];
-        sh.barb = MANY ? modswitch_nu(xb, mo.th) : modswitch_2N(xb);
-    }
+    br_prologue<MANY, kV4Threads>(t, mo.th, tid, sh.bara, sh.barb);
     __syncthreads();
     if (LUT && tv) {   // ACC = (0, X^{2N - barb} tv) as its periodic extension (modarith.h lut_coeff)
         const int e = (k2N - sh.barb) & (k2N - 1);
@@ -251,24 +231,9 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4(V4Args g, 
         const int idx = half ? gct - B : gct;
         const BrInput &in = half ? in1 : in0;
         RowTerms t;
-        t.c = in.c; t.sa = in.sa; t.sb = in.sb; t.sc = 0;
-        t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
-        t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
-        t.za = nullptr; t.zb = nullptr;
-        if constexpr (LUT) {   // the third input (engine.h BrInput): LUT and many-LUT launches only
-            t.sc = in.sc;
-            t.za = in.sc ? in.z_a + (size_t)idx * kn : nullptr; t.zb = in.sc ? in.z_b + idx : nullptr;
-        }
-        if constexpr (MANY)   // one half: output f of ciphertext gct is u sample f B + gct
-            br_v4_body<true, true>(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct,
-                                   lut_table(in.tv, in.lut_index, in.n_lut, idx),
-                                   ManyOut{in.log_nu, in.n_out, u_a + ((size_t)B + gct) * kN, u_b + (size_t)B + gct,
-                                           (size_t)B});
-        else if constexpr (LUT)
-            br_v4_body<true>(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct,
-                             lut_table(in.tv, in.lut_index, in.n_lut, idx));
-        else
-            br_v4_body(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct);
+        row_terms<LUT>(t, in, idx);
+        const LutArgs l = lut_args<LUT, MANY>(in, B, idx, gct, u_a, u_b);
+        br_v4_body<LUT, MANY>(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, l.tv, l.mo);
     }
 }
 
@@ -289,31 +254,10 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4_rows(V4Arg
         used = true;
         const int r = (int)(slot / B), k = (int)(slot - (long)r * B);
         const CircRow row = rows[r];
-        auto wire = [&](int w, const int32_t *&pa, const int32_t *&pb) {
-            if (w < 0) { pa = nullptr; pb = nullptr; return; }
-            const size_t ws = (size_t)w * B + k;
-            pa = wa + ws * kn;
-            pb = wb + ws;
-        };
         RowTerms t;
-        t.c = row.c; t.sa = row.sa; t.sb = row.sb; t.sc = row.sc;
-        wire(row.x, t.xa, t.xb);
-        wire(row.y, t.ya, t.yb);
-        wire(row.z, t.za, t.zb);
-        if constexpr (MANY) {
-            // outputs f >= 1 of a many-LUT row: u rows row.urow + f - 1 (engine.h CircRow)
-            const int32_t *tv = row.lut ? reinterpret_cast<const int32_t *>(rows + r) + row.lut : nullptr;
-            const size_t s1 = (size_t)row.urow * B + k;
-            br_v4_body<true, true>(sh, g, t, mu, u_a + (size_t)slot * kN, u_b + slot, tv,
-                                   ManyOut{row.many & 7, row.many ? (row.many >> 8) & 31 : 1, u_a + s1 * kN, u_b + s1,
-                                           (size_t)B});
-        } else if constexpr (LUT) {
-            // a LUT row's test vector lies row.lut words after its own record (engine.h CircRow)
-            const int32_t *tv = row.lut ? reinterpret_cast<const int32_t *>(rows + r) + row.lut : nullptr;
-            br_v4_body<true>(sh, g, t, mu, u_a + (size_t)slot * kN, u_b + slot, tv);
-        } else {
-            br_v4_body(sh, g, t, mu, u_a + (size_t)slot * kN, u_b + slot);
-        }
+        row_terms(t, row, wa, wb, B, k);
+        const LutArgs l = lut_args<LUT, MANY>(rows + r, row, B, k, u_a, u_b);
+        br_v4_body<LUT, MANY>(sh, g, t, mu, u_a + (size_t)slot * kN, u_b + slot, l.tv, l.mo);
     }
 }
 
@@ -411,92 +355,46 @@ static V4Guard v4_guard(const Guard *guard) {
     return gd;
 }
 
+// MINW (the kernels' first template argument): 1 for the guard launch, 2 for the exact one
 hipError_t launch_blind_rotate_v4(const DeviceKey &key, int B, int halves, const BrInput *in, int32_t mu,
                                   int32_t *u_a, int32_t *u_b, hipStream_t s, const Guard *guard) {
     if (B <= 0) return hipSuccess;
     if (!key.bk_v2) return hipErrorInvalidValue;
+    BrMode mode;   // the guard launch recomputes a flagged ciphertext from the same table
+    if (br_mode(in, halves, &mode) != hipSuccess) return hipErrorInvalidValue;
     const BrInput in1 = halves > 1 ? in[1] : in[0];
     const V4Guard gd = v4_guard(guard);
     const int total = B * halves;
     // guard mode: 256 workgroups scan the flags (B = 1024: 15 -> ~4 us per launch)
     const int grid = gd.flags && total > kGuardGrid ? kGuardGrid : total;
-    // programmable bootstrap: every half carries its tables (n_lut >= 1), or none does; the guard
-    // launch recomputes a flagged ciphertext from the same table
-    const bool lut = in[0].tv != nullptr;
-    if (lut != (in1.tv != nullptr) || (lut && (in[0].n_lut <= 0 || in1.n_lut <= 0))) return hipErrorInvalidValue;
-    // many-LUT (engine.h BrInput): one half, tables, log_nu in [0, 4], n_out in [1, 2^log_nu]
-    const bool many = in[0].n_out != 0;
-    if (many && (!lut || halves != 1 || in[0].log_nu < 0 || in[0].log_nu > 4 || in[0].n_out < 1 ||
-                 in[0].n_out > (1 << in[0].log_nu)))
-        return hipErrorInvalidValue;
-    // third input (engine.h BrInput): only the LUT instantiations read it
-    for (const BrInput *h : {&in[0], &in1})
-        if (h->sc && (!lut || !h->z_a || !h->z_b)) return hipErrorInvalidValue;
-    if (many) {
-        trace_kernel(gd.flags ? "k_blind_rotate_v4(lut-many+guard)" : "k_blind_rotate_v4(lut-many)");
-        if (gd.flags)
-            hipLaunchKernelGGL((k_blind_rotate_v4<1, true, true>), dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B,
-                               total, in[0], in1, mu, u_a, u_b, gd);
-        else
-            hipLaunchKernelGGL((k_blind_rotate_v4<2, true, true>), dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B,
-                               total, in[0], in1, mu, u_a, u_b, gd);
-        return hipGetLastError();
-    }
-    if (lut) {
-        trace_kernel(gd.flags ? "k_blind_rotate_v4(lut+guard)" : "k_blind_rotate_v4(lut)");
-        if (gd.flags)
-            hipLaunchKernelGGL((k_blind_rotate_v4<1, true>), dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B, total,
-                               in[0], in1, mu, u_a, u_b, gd);
-        else
-            hipLaunchKernelGGL((k_blind_rotate_v4<2, true>), dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B, total,
-                               in[0], in1, mu, u_a, u_b, gd);
-        return hipGetLastError();
-    }
-    trace_kernel(gd.flags ? "k_blind_rotate_v4(guard)" : "k_blind_rotate_v4");
-    if (gd.flags)
-        hipLaunchKernelGGL(k_blind_rotate_v4<1>, dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B, total, in[0],
-                           in1, mu, u_a, u_b, gd);
-    else
-        hipLaunchKernelGGL(k_blind_rotate_v4<2>, dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B, total, in[0],
-                           in1, mu, u_a, u_b, gd);
+    trace_kernel(KernelLabel("k_blind_rotate_v4", mode, {gd.flags ? "guard" : nullptr}).s);
+    with_mode(mode, [&](auto m) {
+        with_flag(gd.flags != nullptr, [&](auto f) {
+            hipLaunchKernelGGL((k_blind_rotate_v4<decltype(f)::value ? 1 : 2, mode_lut(decltype(m)::value),
+                                                  mode_many(decltype(m)::value)>),
+                               dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B, total, in[0], in1, mu, u_a, u_b, gd);
+        });
+    });
     return hipGetLastError();
 }
 
 hipError_t launch_blind_rotate_v4_rows(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
-                                       const Guard *guard) {
+                                       BrMode mode, const Guard *guard) {
     if (B <= 0 || nrows <= 0) return hipSuccess;
     if (!key.bk_v2) return hipErrorInvalidValue;
     const V4Guard gd = v4_guard(guard);
     const long total = (long)B * nrows;
     const long grid = gd.flags && total > kGuardGrid ? kGuardGrid : total < 0x7fffffffL ? total : 0x7fffffffL;
-    if (guard && guard->many_rows) {   // some row is a many-LUT row (engine.h Guard)
-        trace_kernel(gd.flags ? "k_blind_rotate_v4_rows(lut-many+guard)" : "k_blind_rotate_v4_rows(lut-many)");
-        if (gd.flags)
-            hipLaunchKernelGGL((k_blind_rotate_v4_rows<1, true, true>), dim3((unsigned)grid), dim3(kV4Threads), 0, s,
-                               v4_args(key), B, total, rows, wa, wb, mu, u_a, u_b, gd);
-        else
-            hipLaunchKernelGGL((k_blind_rotate_v4_rows<2, true, true>), dim3((unsigned)grid), dim3(kV4Threads), 0, s,
-                               v4_args(key), B, total, rows, wa, wb, mu, u_a, u_b, gd);
-        return hipGetLastError();
-    }
-    if (guard && guard->lut_rows) {   // some row carries a test vector (engine.h Guard)
-        trace_kernel(gd.flags ? "k_blind_rotate_v4_rows(lut+guard)" : "k_blind_rotate_v4_rows(lut)");
-        if (gd.flags)
-            hipLaunchKernelGGL((k_blind_rotate_v4_rows<1, true>), dim3((unsigned)grid), dim3(kV4Threads), 0, s,
-                               v4_args(key), B, total, rows, wa, wb, mu, u_a, u_b, gd);
-        else
-            hipLaunchKernelGGL((k_blind_rotate_v4_rows<2, true>), dim3((unsigned)grid), dim3(kV4Threads), 0, s,
-                               v4_args(key), B, total, rows, wa, wb, mu, u_a, u_b, gd);
-        return hipGetLastError();
-    }
-    trace_kernel(gd.flags ? "k_blind_rotate_v4_rows(guard)" : "k_blind_rotate_v4_rows");
-    if (gd.flags)
-        hipLaunchKernelGGL(k_blind_rotate_v4_rows<1>, dim3((unsigned)grid), dim3(kV4Threads), 0, s, v4_args(key), B,
-                           total, rows, wa, wb, mu, u_a, u_b, gd);
-    else
-        hipLaunchKernelGGL(k_blind_rotate_v4_rows<2>, dim3((unsigned)grid), dim3(kV4Threads), 0, s, v4_args(key), B,
-                           total, rows, wa, wb, mu, u_a, u_b, gd);
+    trace_kernel(KernelLabel("k_blind_rotate_v4_rows", mode, {gd.flags ? "guard" : nullptr}).s);
+    with_mode(mode, [&](auto m) {
+        with_flag(gd.flags != nullptr, [&](auto f) {
+            hipLaunchKernelGGL((k_blind_rotate_v4_rows<decltype(f)::value ? 1 : 2, mode_lut(decltype(m)::value),
+                                                       mode_many(decltype(m)::value)>),
+                               dim3((unsigned)grid), dim3(kV4Threads), 0, s, v4_args(key), B, total, rows, wa, wb, mu, u_a,
+                               u_b, gd);
+        });
+    });
     return hipGetLastError();
 }
 

@@ -38,8 +38,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <vector>
-#include "engine.h"
-#include "modarith.h"
+#include "br_common.h"
 #include "fft_wave.h"
 
 namespace tfhe_amd {
@@ -374,7 +373,7 @@ __device__ __forceinline__ void cmux_v6(V6Ct &sh, const double2 *shtw, const V6A
 // 2^mo.th and the epilogue extracts the coefficients 0 .. mo.n_out - 1 (modarith.h ManyOut); the
 // 500 steps between them are the same.
 template <int WAVES, bool RREG, int C = 1, bool PS = false, bool LUT = false, bool MANY = false>
-__device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args &g, const RowTerms6 &t, int32_t mu,
+__device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args &g, const RowTerms &t, int32_t mu,
                                            int32_t *__restrict__ ua, int32_t *__restrict__ ub, size_t slot,
                                            bool live = true, const int32_t *__restrict__ tv = nullptr,
                                            const ManyOut &mo = ManyOut{}) {
@@ -390,19 +389,7 @@ __device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args
         g_v6_wg[wg][5] = hwreg_xcc_id();
     }
 #endif
-    // gate prologue + modulus switching (lwe-bootstrapping-functions-fft.cu:1851-1858)
-    for (int i = tid; i < kn; i += kV6Threads) {
-        uint32_t x = t.xa ? (uint32_t)t.sa * (uint32_t)t.xa[i] : 0u;
-        if (t.ya) x += (uint32_t)t.sb * (uint32_t)t.ya[i];
-        if (t.za) x += (uint32_t)t.sc * (uint32_t)t.za[i];
-        sh.bara[i] = (short)(MANY ? modswitch_nu(x, mo.th) : modswitch_2N(x));
-    }
-    if (tid == 0) {
-        uint32_t xb = (uint32_t)t.c + (t.xb ? (uint32_t)t.sa * (uint32_t)t.xb[0] : 0u);
-        if (t.yb) xb += (uint32_t)t.sb * (uint32_t)t.yb[0];
-        if (t.zb) xb += (uint32_t)t.sc * (uint32_t)t.zb[0];
-        sh.barb = MANY ? modswitch_nu(xb, mo.th) : modswitch_2N(xb);
-    }
+    br_prologue<MANY, kV6Threads>(t, mo.th, tid, sh.bara, sh.barb);
     if (tid < 2) sh.sync[tid] = 0;
     for (int e = threadIdx.x; e < kT8Words; e += C * kV6Threads) shtw[e] = g.tw[t8_src(e)];
     const Tw4 tA = load_tw_sgpr(g.tw);
@@ -507,25 +494,11 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6(V6Args g,
     const int half = gct >= B;
     const int idx = half ? gct - B : gct;
     const BrInput &in = half ? in1 : in0;
-    RowTerms6 t;
-    t.c = in.c; t.sa = in.sa; t.sb = in.sb; t.sc = 0;
-    t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
-    t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
-    t.za = nullptr; t.zb = nullptr;
-    if constexpr (LUT) {   // the third input (engine.h BrInput): LUT and many-LUT launches only
-        t.sc = in.sc;
-        t.za = in.sc ? in.z_a + (size_t)idx * kn : nullptr; t.zb = in.sc ? in.z_b + idx : nullptr;
-    }
-    if constexpr (MANY)   // one half: output f of ciphertext gct is u sample f B + gct
-        br_v6_body<WAVES, RREG, 1, false, true, true>(
-            sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct, true,
-            lut_table(in.tv, in.lut_index, in.n_lut, idx),
-            ManyOut{in.log_nu, in.n_out, u_a + ((size_t)B + gct) * kN, u_b + (size_t)B + gct, (size_t)B});
-    else if constexpr (LUT)
-        br_v6_body<WAVES, RREG, 1, false, true>(sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct,
-                                                true, lut_table(in.tv, in.lut_index, in.n_lut, idx));
-    else
-        br_v6_body<WAVES, RREG>(sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct);
+    RowTerms t;
+    row_terms<LUT>(t, in, idx);
+    const LutArgs l = lut_args<LUT, MANY>(in, B, idx, gct, u_a, u_b);
+    br_v6_body<WAVES, RREG, 1, false, LUT, MANY>(sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct,
+                                                 (size_t)gct, true, l.tv, l.mo);
 }
 
 // two ciphertexts per workgroup (4 waves): the dispatcher spreads a 4-wave workgroup over the
@@ -544,26 +517,12 @@ __global__ __launch_bounds__(2 * kV6Threads, WAVES) void k_blind_rotate_v6p(V6Ar
     const int half = gct >= B;
     const int idx = half ? gct - B : gct;
     const BrInput &in = half ? in1 : in0;
-    RowTerms6 t;
-    t.c = in.c; t.sa = in.sa; t.sb = in.sb; t.sc = 0;
-    t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
-    t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
-    t.za = nullptr; t.zb = nullptr;
-    if constexpr (LUT) {   // the third input (engine.h BrInput): LUT and many-LUT launches only
-        t.sc = in.sc;
-        t.za = in.sc ? in.z_a + (size_t)idx * kn : nullptr; t.zb = in.sc ? in.z_b + idx : nullptr;
-    }
+    RowTerms t;
+    row_terms<LUT>(t, in, idx);
     // (the padding ciphertext repeats the last live one, table included)
-    if constexpr (MANY)
-        br_v6_body<WAVES, true, 2, PS, true, true>(
-            sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct, live,
-            lut_table(in.tv, in.lut_index, in.n_lut, idx),
-            ManyOut{in.log_nu, in.n_out, u_a + ((size_t)B + gct) * kN, u_b + (size_t)B + gct, (size_t)B});
-    else if constexpr (LUT)
-        br_v6_body<WAVES, true, 2, PS, true>(sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct,
-                                             live, lut_table(in.tv, in.lut_index, in.n_lut, idx));
-    else
-        br_v6_body<WAVES, true, 2, PS>(sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct, live);
+    const LutArgs l = lut_args<LUT, MANY>(in, B, idx, gct, u_a, u_b);
+    br_v6_body<WAVES, true, 2, PS, LUT, MANY>(sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct,
+                                              live, l.tv, l.mo);
 }
 
 template <int WAVES, bool RREG, bool LUT = false, bool MANY = false>
@@ -577,33 +536,12 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6_rows(V6Ar
     const long flat = base + blockIdx.x;          // row-major (row, instance)
     const int r = (int)(flat / B), k = (int)(flat - (long)r * B);
     const CircRow row = rows[r];
-    auto wire = [&](int wi, const int32_t *&pa, const int32_t *&pb) {
-        if (wi < 0) { pa = nullptr; pb = nullptr; return; }
-        const size_t slot = (size_t)wi * B + k;
-        pa = wa + slot * kn;
-        pb = wb + slot;
-    };
-    RowTerms6 t;
-    t.c = row.c; t.sa = row.sa; t.sb = row.sb; t.sc = row.sc;
-    wire(row.x, t.xa, t.xb);
-    wire(row.y, t.ya, t.yb);
-    wire(row.z, t.za, t.zb);
+    RowTerms t;
+    row_terms(t, row, wa, wb, B, k);
     const size_t slot = (size_t)r * B + k;
-    if constexpr (MANY) {
-        // outputs f >= 1 of a many-LUT row: u rows row.urow + f - 1 (engine.h CircRow); every other
-        // row of the launch is th = 0, n_out = 1
-        const int32_t *tv = row.lut ? reinterpret_cast<const int32_t *>(rows + r) + row.lut : nullptr;
-        const size_t s1 = (size_t)row.urow * B + k;
-        br_v6_body<WAVES, RREG, 1, false, true, true>(
-            sh.ct[0], sh.tw, g, t, mu, u_a + slot * kN, u_b + slot, slot, true, tv,
-            ManyOut{row.many & 7, row.many ? (row.many >> 8) & 31 : 1, u_a + s1 * kN, u_b + s1, (size_t)B});
-    } else if constexpr (LUT) {
-        // a LUT row's test vector lies row.lut words after its own record (engine.h CircRow)
-        const int32_t *tv = row.lut ? reinterpret_cast<const int32_t *>(rows + r) + row.lut : nullptr;
-        br_v6_body<WAVES, RREG, 1, false, true>(sh.ct[0], sh.tw, g, t, mu, u_a + slot * kN, u_b + slot, slot, true, tv);
-    } else {
-        br_v6_body<WAVES, RREG>(sh.ct[0], sh.tw, g, t, mu, u_a + slot * kN, u_b + slot, slot);
-    }
+    const LutArgs l = lut_args<LUT, MANY>(rows + r, row, B, k, u_a, u_b);
+    br_v6_body<WAVES, RREG, 1, false, LUT, MANY>(sh.ct[0], sh.tw, g, t, mu, u_a + slot * kN, u_b + slot, slot, true, l.tv,
+                                                 l.mo);
 }
 
 template <bool RREG>
@@ -786,124 +724,62 @@ static V6Args v6_args(const DeviceKey &key, long wgs, const Guard *guard = nullp
     return g;
 }
 
-// one chunk of a programmable-bootstrap launch: the constant path's launch forms, LUT (MANY:
-// many-LUT) instantiations
-template <bool MANY>
-static void v6_launch_lut(const DeviceKey &key, long n, int B, long total, long base, const BrInput &in0,
-                          const BrInput &in1, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
-                          const Guard *guard) {
-    if (v6_pair(key, n)) {
-        const long wgs = (n + 1) / 2;
-        if (v6p_pairsync() && guard && guard->flags) {
-            trace_kernel(MANY ? "k_blind_rotate_v6p(lut-many+paired+reg-rotation+pair-sync)"
-                              : "k_blind_rotate_v6p(lut+paired+reg-rotation+pair-sync)");
-            hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, true, true, MANY>), dim3((unsigned)wgs),
-                               dim3(2 * kV6Threads), 0, s, v6_args(key, wgs, guard, true), B, (int)total, (int)base,
-                               in0, in1, mu, u_a, u_b);
-        } else {
-            trace_kernel(MANY ? "k_blind_rotate_v6p(lut-many+paired+reg-rotation)"
-                              : "k_blind_rotate_v6p(lut+paired+reg-rotation)");
-            hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, false, true, MANY>), dim3((unsigned)wgs),
-                               dim3(2 * kV6Threads), 0, s, v6_args(key, wgs, guard, true), B, (int)total, (int)base,
-                               in0, in1, mu, u_a, u_b);
-        }
-    } else if (v6_rreg(key, n)) {
-        trace_kernel(MANY ? "k_blind_rotate_v6(lut-many+reg-rotation)" : "k_blind_rotate_v6(lut+reg-rotation)");
-        hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, true, true, MANY>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
-                           v6_args(key, n, guard), B, (int)base, in0, in1, mu, u_a, u_b);
-    } else {
-        trace_kernel(MANY ? "k_blind_rotate_v6(lut-many+lds-rotation)" : "k_blind_rotate_v6(lut+lds-rotation)");
-        hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, false, true, MANY>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
-                           v6_args(key, n, guard), B, (int)base, in0, in1, mu, u_a, u_b);
-    }
-}
-
 hipError_t launch_blind_rotate_v6(const DeviceKey &key, int B, int halves, const BrInput *in, int32_t mu,
                                   int32_t *u_a, int32_t *u_b, hipStream_t s, const Guard *guard) {
     if (B <= 0) return hipSuccess;
     if (!key.bk_fft) return hipErrorInvalidValue;
+    BrMode mode;
+    if (br_mode(in, halves, &mode) != hipSuccess) return hipErrorInvalidValue;
     const BrInput in1 = halves > 1 ? in[1] : in[0];
     const long total = (long)B * halves, chunk = v6_chunk(key);
-    // programmable bootstrap: every half carries its tables (n_lut >= 1), or none does
-    const bool lut = in[0].tv != nullptr;
-    if (lut != (in1.tv != nullptr) || (lut && (in[0].n_lut <= 0 || in1.n_lut <= 0))) return hipErrorInvalidValue;
-    // many-LUT (engine.h BrInput): one half, tables, log_nu in [0, 4], n_out in [1, 2^log_nu]
-    const bool many = in[0].n_out != 0;
-    if (many && (!lut || halves != 1 || in[0].log_nu < 0 || in[0].log_nu > 4 || in[0].n_out < 1 ||
-                 in[0].n_out > (1 << in[0].log_nu)))
-        return hipErrorInvalidValue;
-    // third input (engine.h BrInput): only the LUT instantiations read it
-    for (const BrInput *h : {&in[0], &in1})
-        if (h->sc && (!lut || !h->z_a || !h->z_b)) return hipErrorInvalidValue;
     for (long base = 0; base < total; base += chunk) {
         const long n = total - base < chunk ? total - base : chunk;
-        if (lut) {
-            if (many) v6_launch_lut<true>(key, n, B, total, base, in[0], in1, mu, u_a, u_b, s, guard);
-            else v6_launch_lut<false>(key, n, B, total, base, in[0], in1, mu, u_a, u_b, s, guard);
-        } else if (v6_pair(key, n)) {
-            const long wgs = (n + 1) / 2;
-            // the pair sync's bounded poll hands a ciphertext whose partner never arrives to the
-            // guard (bad flag -> exact recomputation): only with guard flags to hand it to
-            if (v6p_pairsync() && guard && guard->flags) {
-                trace_kernel("k_blind_rotate_v6p(paired+reg-rotation+pair-sync)");
-                hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, true>), dim3((unsigned)wgs), dim3(2 * kV6Threads), 0, s,
-                                   v6_args(key, wgs, guard, true), B, (int)total, (int)base, in[0], in1, mu, u_a, u_b);
-            } else {
-                trace_kernel("k_blind_rotate_v6p(paired+reg-rotation)");
-                hipLaunchKernelGGL(k_blind_rotate_v6p<kV6Waves>, dim3((unsigned)wgs), dim3(2 * kV6Threads), 0, s,
-                                   v6_args(key, wgs, guard, true), B, (int)total, (int)base, in[0], in1, mu, u_a, u_b);
-            }
-        } else {
-            trace_kernel(v6_rreg(key, n) ? "k_blind_rotate_v6(reg-rotation)" : "k_blind_rotate_v6(lds-rotation)");
-            if (v6_rreg(key, n))
-                hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, true>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
-                                   v6_args(key, n, guard), B, (int)base, in[0], in1, mu, u_a, u_b);
-            else
-                hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, false>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
-                                   v6_args(key, n, guard), B, (int)base, in[0], in1, mu, u_a, u_b);
-        }
+        const bool paired = v6_pair(key, n), rreg = paired || v6_rreg(key, n);
+        // the pair sync's bounded poll hands a ciphertext whose partner never arrives to the
+        // guard (bad flag -> exact recomputation): only with guard flags to hand it to
+        const bool ps = paired && v6p_pairsync() && guard && guard->flags;
+        const long wgs = paired ? (n + 1) / 2 : n;
+        const V6Args g = v6_args(key, wgs, guard, paired);
+        trace_kernel(KernelLabel(paired ? "k_blind_rotate_v6p" : "k_blind_rotate_v6", mode,
+                                 {paired ? "paired" : nullptr, rreg ? "reg-rotation" : "lds-rotation",
+                                  ps ? "pair-sync" : nullptr})
+                         .s);
+        // the kernel's second template argument: the pair sync of the paired kernel, the rotation of the other
+        with_mode(mode, [&](auto m) {
+            with_flag(paired ? ps : rreg, [&](auto f) {
+                constexpr bool F = decltype(f)::value, LUT = mode_lut(decltype(m)::value),
+                               MANY = mode_many(decltype(m)::value);
+                if (paired)
+                    hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, F, LUT, MANY>), dim3((unsigned)wgs),
+                                       dim3(2 * kV6Threads), 0, s, g, B, (int)total, (int)base, in[0], in1, mu, u_a, u_b);
+                else
+                    hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, F, LUT, MANY>), dim3((unsigned)wgs),
+                                       dim3(kV6Threads), 0, s, g, B, (int)base, in[0], in1, mu, u_a, u_b);
+            });
+        });
     }
     return hipGetLastError();
 }
 
 hipError_t launch_blind_rotate_v6_rows(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
-                                       const Guard *guard) {
+                                       BrMode mode, const Guard *guard) {
     if (B <= 0 || nrows <= 0) return hipSuccess;
     if (!key.bk_fft) return hipErrorInvalidValue;
     const long total = (long)B * nrows, chunk = v6_chunk(key);
     for (long base = 0; base < total; base += chunk) {
         const long n = total - base < chunk ? total - base : chunk;
         if (n > 0x7fffffffL) return hipErrorInvalidValue;
-        if (guard && guard->many_rows) {   // some row is a many-LUT row (engine.h Guard)
-            trace_kernel(v6_rreg(key, n) ? "k_blind_rotate_v6_rows(lut-many+reg-rotation)"
-                                         : "k_blind_rotate_v6_rows(lut-many+lds-rotation)");
-            if (v6_rreg(key, n))
-                hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, true, true, true>), dim3((unsigned)n),
-                                   dim3(kV6Threads), 0, s, v6_args(key, n, guard), B, base, rows, wa, wb, mu, u_a, u_b);
-            else
-                hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, false, true, true>), dim3((unsigned)n),
-                                   dim3(kV6Threads), 0, s, v6_args(key, n, guard), B, base, rows, wa, wb, mu, u_a, u_b);
-            continue;
-        }
-        if (guard && guard->lut_rows) {   // some row carries a test vector (engine.h Guard)
-            trace_kernel(v6_rreg(key, n) ? "k_blind_rotate_v6_rows(lut+reg-rotation)"
-                                         : "k_blind_rotate_v6_rows(lut+lds-rotation)");
-            if (v6_rreg(key, n))
-                hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, true, true>), dim3((unsigned)n), dim3(kV6Threads), 0,
-                                   s, v6_args(key, n, guard), B, base, rows, wa, wb, mu, u_a, u_b);
-            else
-                hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, false, true>), dim3((unsigned)n), dim3(kV6Threads), 0,
-                                   s, v6_args(key, n, guard), B, base, rows, wa, wb, mu, u_a, u_b);
-            continue;
-        }
-        trace_kernel(v6_rreg(key, n) ? "k_blind_rotate_v6_rows(reg-rotation)" : "k_blind_rotate_v6_rows(lds-rotation)");
-        if (v6_rreg(key, n))
-            hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, true>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
-                               v6_args(key, n, guard), B, base, rows, wa, wb, mu, u_a, u_b);
-        else
-            hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, false>), dim3((unsigned)n), dim3(kV6Threads), 0, s,
-                               v6_args(key, n, guard), B, base, rows, wa, wb, mu, u_a, u_b);
+        const bool rreg = v6_rreg(key, n);
+        trace_kernel(KernelLabel("k_blind_rotate_v6_rows", mode, {rreg ? "reg-rotation" : "lds-rotation"}).s);
+        with_mode(mode, [&](auto m) {
+            with_flag(rreg, [&](auto f) {
+                hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, decltype(f)::value, mode_lut(decltype(m)::value),
+                                                           mode_many(decltype(m)::value)>),
+                                   dim3((unsigned)n), dim3(kV6Threads), 0, s, v6_args(key, n, guard), B, base, rows, wa, wb,
+                                   mu, u_a, u_b);
+            });
+        });
     }
     return hipGetLastError();
 }
@@ -912,13 +788,12 @@ hipError_t launch_blind_rotate_v6_debug(const DeviceKey &key, int B, int iters, 
                                         hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (iters < 0 || iters > kn || !key.bk_fft) return hipErrorInvalidValue;
-    trace_kernel(v6_rreg(key, B) ? "k_blind_rotate_v6_debug(reg-rotation)" : "k_blind_rotate_v6_debug(lds-rotation)");
-    if (v6_rreg(key, B))
-        hipLaunchKernelGGL(k_blind_rotate_v6_debug<true>, dim3(B), dim3(kV6Threads), 0, s, v6_args(key, 0), iters, acc,
-                           bara);
-    else
-        hipLaunchKernelGGL(k_blind_rotate_v6_debug<false>, dim3(B), dim3(kV6Threads), 0, s, v6_args(key, 0), iters,
-                           acc, bara);
+    const bool rreg = v6_rreg(key, B);
+    trace_kernel(KernelLabel("k_blind_rotate_v6_debug", BrMode::Const, {rreg ? "reg-rotation" : "lds-rotation"}).s);
+    with_flag(rreg, [&](auto f) {
+        hipLaunchKernelGGL(k_blind_rotate_v6_debug<decltype(f)::value>, dim3(B), dim3(kV6Threads), 0, s, v6_args(key, 0),
+                           iters, acc, bara);
+    });
     return hipGetLastError();
 }
 

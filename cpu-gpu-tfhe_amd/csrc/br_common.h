@@ -1,0 +1,145 @@
+// br_common.h — what the two blind-rotation generations (blind_rotate_v6.hip, blind_rotate_v4.hip)
+// share: the device-side input decoding and gate prologue, and the launchers' dispatch from a
+// launch's runtime choices to a kernel instantiation and its trace name.
+#pragma once
+#include <cstdio>
+#include <initializer_list>
+#include <type_traits>
+#include "engine.h"
+#include "modarith.h"
+
+namespace tfhe_amd {
+
+// ------------------------------------------------------------------ device side
+
+// The linear combination x = (0, c) + sa X + sb Y + sc Z that feeds one blind rotation (gate
+// prologues boot-gates.cu:98-448; a circuit row adds a third input for MAJ / XOR3).
+struct RowTerms {
+    int32_t c, sa, sb, sc;
+    const int32_t *xa, *xb, *ya, *yb, *za, *zb;   // a rows (kn) and b words; y / z may be null
+};
+
+// ciphertext idx of a gate-batch input.  The third input (engine.h BrInput) is read only by the
+// LUT and many-LUT instantiations; the constant kernels keep two inputs.
+// (in by value, here and in lut_args: the kernels pick one of two kernel arguments by half, and
+// through a reference to that choice the compiler loads both records whole and selects field by
+// field, which in the v4 kernels spills 40 - 90 more scalar registers to lanes; the copy of the
+// chosen record is read through one selected pointer, as the kernels' own code was)
+template <bool LUT>
+__device__ __forceinline__ void row_terms(RowTerms &t, const BrInput in, int idx) {
+    t.c = in.c; t.sa = in.sa; t.sb = in.sb; t.sc = 0;
+    t.xa = in.x_a + (size_t)idx * kn; t.xb = in.x_b + idx;
+    t.ya = in.sb ? in.y_a + (size_t)idx * kn : nullptr; t.yb = in.sb ? in.y_b + idx : nullptr;
+    t.za = nullptr; t.zb = nullptr;
+    if constexpr (LUT) {
+        t.sc = in.sc;
+        t.za = in.sc ? in.z_a + (size_t)idx * kn : nullptr; t.zb = in.sc ? in.z_b + idx : nullptr;
+    }
+}
+// instance k of a circuit row over the wires [W][B] (wire index -1: absent)
+__device__ __forceinline__ void row_terms(RowTerms &t, const CircRow &row, const int32_t *wa, const int32_t *wb, int B,
+                                          int k) {
+    auto wire = [&](int w, const int32_t *&pa, const int32_t *&pb) {
+        if (w < 0) { pa = nullptr; pb = nullptr; return; }
+        const size_t ws = (size_t)w * B + k;
+        pa = wa + ws * kn;
+        pb = wb + ws;
+    };
+    t.c = row.c; t.sa = row.sa; t.sb = row.sb; t.sc = row.sc;
+    wire(row.x, t.xa, t.xb);
+    wire(row.y, t.ya, t.yb);
+    wire(row.z, t.za, t.zb);
+}
+
+// The test vector and the extra outputs of one ciphertext.  Compile-time null / default for the
+// constant instantiations, which form no table address.
+struct LutArgs {
+    const int32_t *tv = nullptr;
+    ManyOut mo;
+};
+// gate batch: ciphertext idx of its half, gct of the launch.  Many-LUT launches have one half:
+// output f of ciphertext gct is u sample f B + gct.
+template <bool LUT, bool MANY>
+__device__ __forceinline__ LutArgs lut_args(const BrInput in, int B, int idx, int gct, int32_t *u_a, int32_t *u_b) {
+    LutArgs l;
+    if constexpr (LUT) l.tv = lut_table(in.tv, in.lut_index, in.n_lut, idx);
+    if constexpr (MANY)
+        l.mo = ManyOut{in.log_nu, in.n_out, u_a + ((size_t)B + gct) * kN, u_b + (size_t)B + gct, (size_t)B};
+    return l;
+}
+// circuit row `row` (the record at `rec`), instance k: a LUT row's test vector lies row.lut words
+// after its own record; outputs f >= 1 of a many-LUT row go to the u rows row.urow + f - 1, every
+// other row of a many-LUT launch is th = 0, n_out = 1 (engine.h CircRow)
+template <bool LUT, bool MANY>
+__device__ __forceinline__ LutArgs lut_args(const CircRow *rec, const CircRow &row, int B, int k, int32_t *u_a,
+                                            int32_t *u_b) {
+    LutArgs l;
+    if constexpr (LUT) l.tv = row.lut ? reinterpret_cast<const int32_t *>(rec) + row.lut : nullptr;
+    if constexpr (MANY) {
+        const size_t s1 = (size_t)row.urow * B + k;
+        l.mo = ManyOut{row.many & 7, row.many ? (row.many >> 8) & 31 : 1, u_a + s1 * kN, u_b + s1, (size_t)B};
+    }
+    return l;
+}
+
+// gate prologue + modulus switching (lwe-bootstrapping-functions-fft.cu:1851-1858) by the THREADS
+// threads of one ciphertext: bara[0 .. kn) and barb, rotation amounts < 2N (MANY: multiples of 2^th)
+template <bool MANY, int THREADS, typename T>
+__device__ __forceinline__ void br_prologue(const RowTerms &t, int th, int tid, T *bara, int &barb) {
+    for (int i = tid; i < kn; i += THREADS) {
+        uint32_t x = t.xa ? (uint32_t)t.sa * (uint32_t)t.xa[i] : 0u;
+        if (t.ya) x += (uint32_t)t.sb * (uint32_t)t.ya[i];
+        if (t.za) x += (uint32_t)t.sc * (uint32_t)t.za[i];
+        bara[i] = (T)(MANY ? modswitch_nu(x, th) : modswitch_2N(x));
+    }
+    if (tid == 0) {
+        uint32_t xb = (uint32_t)t.c + (t.xb ? (uint32_t)t.sa * (uint32_t)t.xb[0] : 0u);
+        if (t.yb) xb += (uint32_t)t.sb * (uint32_t)t.yb[0];
+        if (t.zb) xb += (uint32_t)t.sc * (uint32_t)t.zb[0];
+        barb = MANY ? modswitch_nu(xb, th) : modswitch_2N(xb);
+    }
+}
+
+// ------------------------------------------------------------------ launchers
+
+namespace {   // host helpers of the two launcher files, not library symbols
+
+// A launcher's runtime choices as compile-time constants: f is called with the mode, or the flag,
+// as a std::integral_constant, and names the kernel instantiation from it.
+template <class F>
+void with_mode(BrMode mode, F &&f) {
+    switch (mode) {
+    case BrMode::Many: return f(std::integral_constant<BrMode, BrMode::Many>{});
+    case BrMode::Lut: return f(std::integral_constant<BrMode, BrMode::Lut>{});
+    default: return f(std::integral_constant<BrMode, BrMode::Const>{});
+    }
+}
+template <class F>
+void with_flag(bool flag, F &&f) {
+    return flag ? f(std::true_type{}) : f(std::false_type{});
+}
+constexpr bool mode_lut(BrMode m) { return m != BrMode::Const; }
+constexpr bool mode_many(BrMode m) { return m == BrMode::Many; }
+
+// The trace name of a launch (engine.h trace_kernel), from the same choices: the kernel's name,
+// then in parentheses the mode (lut / lut-many; nothing for the constant form) and the form's
+// non-null parts, joined by '+'; the bare name when there is nothing to say.
+struct KernelLabel {
+    char s[96];
+    KernelLabel(const char *name, BrMode mode, std::initializer_list<const char *> form) {
+        size_t n = (size_t)snprintf(s, sizeof s, "%s", name);
+        const char *sep = "(";
+        auto add = [&](const char *part) {
+            if (!part || n >= sizeof s) return;
+            n += (size_t)snprintf(s + n, sizeof s - n, "%s%s", sep, part);
+            sep = "+";
+        };
+        add(mode == BrMode::Many ? "lut-many" : mode == BrMode::Lut ? "lut" : nullptr);
+        for (const char *part : form) add(part);
+        if (*sep == '+' && n < sizeof s) snprintf(s + n, sizeof s - n, ")");
+    }
+};
+
+}  // namespace
+
+}  // namespace tfhe_amd

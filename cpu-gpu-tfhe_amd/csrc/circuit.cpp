@@ -598,11 +598,10 @@ int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int de
     const CircLin *d_lin = (const CircLin *)(d_ks + c->ks.size());
     for (const auto &lv : c->levels) {
         if (lv.nrows) {
-            Guard gd = guard_stats ? Guard{st->u_flags, guard_stats} : Guard{};
-            gd.lut_rows = lv.lut;   // the launch takes the rows kernels' LUT instantiation
-            gd.many_rows = lv.many;  // ... or their many-LUT instantiation
-            const hipError_t e =
-                launch_blind_rotate_rows(key, B, lv.nrows, d_rows + lv.row0, wa, wb, kE8, st->u_a, st->u_b, s, &gd);
+            const Guard gd = guard_stats ? Guard{st->u_flags, guard_stats} : Guard{};
+            const BrMode mode = lv.many ? BrMode::Many : lv.lut ? BrMode::Lut : BrMode::Const;
+            const hipError_t e = launch_blind_rotate_rows(key, B, lv.nrows, d_rows + lv.row0, wa, wb, kE8, st->u_a,
+                                                          st->u_b, s, mode, &gd);
             if (e != hipSuccess) return TFHE_AMD_E_HIP;
             if (launch_keyswitch_rows(key, B, lv.nks, d_ks + lv.ks0, st->u_a, st->u_b, wa, wb, s) != hipSuccess)
                 return TFHE_AMD_E_HIP;

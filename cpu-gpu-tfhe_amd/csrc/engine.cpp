@@ -131,20 +131,11 @@ static hipError_t run_br(const DeviceKey &key, int B, int halves, const BrInput 
 
 hipError_t launch_blind_rotate_rows(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                     const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
-                                    const Guard *guard) {
-    switch (br_version()) {
-    case 4: {
-        // no flags: not guard mode, LUT (many-LUT) rows present
-        const Guard lut_only{nullptr, nullptr, true, guard && guard->many_rows};
-        return launch_blind_rotate_v4_rows(key, B, nrows, rows, wa, wb, mu, u_a, u_b, s,
-                                           guard && guard->lut_rows ? &lut_only : nullptr);
-    }
-    default: {
-        hipError_t e = launch_blind_rotate_v6_rows(key, B, nrows, rows, wa, wb, mu, u_a, u_b, s, guard);
-        if (e != hipSuccess || !guard || !guard->flags) return e;
-        return launch_blind_rotate_v4_rows(key, B, nrows, rows, wa, wb, mu, u_a, u_b, s, guard);
-    }
-    }
+                                    BrMode mode, const Guard *guard) {
+    if (br_version() == 4) return launch_blind_rotate_v4_rows(key, B, nrows, rows, wa, wb, mu, u_a, u_b, s, mode);
+    hipError_t e = launch_blind_rotate_v6_rows(key, B, nrows, rows, wa, wb, mu, u_a, u_b, s, mode, guard);
+    if (e != hipSuccess || !guard || !guard->flags) return e;
+    return launch_blind_rotate_v4_rows(key, B, nrows, rows, wa, wb, mu, u_a, u_b, s, mode, guard);
 }
 
 }  // namespace tfhe_amd
@@ -622,6 +613,43 @@ static Guard ctx_guard(TfheAmdContext *c) {
     return c->gflags && c->gstats ? Guard{c->gflags, c->gstats} : Guard{};
 }
 
+// The frame of the device entry points: B x halves blind rotations from in[0 .. halves) with mu into
+// (u_a, u_b) — null: the context's scratch c->u_a / c->u_b — then, for n_ks > 0, the key switch of
+// n_ks extracted samples into (res_a, res_b); halves = 2 is the MUX form, KS(u1 + u2 + (0, add_b)).
+// `slots`: the ciphertext slots to reserve (guard flags per ciphertext, scratch samples per output).
+// The callers have checked their arguments; the order lock -> device -> trace -> reserve -> fence is
+// what every entry point relies on.
+static int batch_dev(TfheAmdContext *c, void *stream, int slots, int B, int halves, const BrInput *in, int32_t mu,
+                     int32_t *u_a, int32_t *u_b, int n_ks = 0, int32_t add_b = 0, int32_t *res_a = nullptr,
+                     int32_t *res_b = nullptr) {
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceScope dev_scope(c->device);
+    HIPCHK(dev_scope.rc);
+    TraceScope trace(c);
+    int rc = tfhe_amd_reserve(c, slots);
+    if (rc) return rc;
+    HIPCHK(c->fence.acquire(s));
+    if (!u_a) {
+        u_a = c->u_a;
+        u_b = c->u_b;
+    }
+    {
+        ProfScope ps(c, s, true);
+        const Guard gd = ctx_guard(c);
+        HIPCHK(run_br(c->key, B, halves, in, mu, u_a, u_b, s, &gd));
+    }
+    if (n_ks > 0) {
+        ProfScope ps(c, s, false);   // (closes behind the fence's event, as the gate path's always did)
+        HIPCHK(launch_keyswitch(c->key, n_ks, u_a, u_b, halves > 1 ? u_a + (size_t)B * kN : nullptr,
+                                halves > 1 ? u_b + B : nullptr, add_b, res_a, res_b, s));
+        HIPCHK(c->fence.done(s));
+        return TFHE_AMD_OK;
+    }
+    HIPCHK(c->fence.done(s));
+    return TFHE_AMD_OK;
+}
+
 extern "C" int tfhe_amd_gate_batch_dev(TfheAmdContext *c, int gate, int B, int32_t *res_a, int32_t *res_b,
                                        const int32_t *ca_a, const int32_t *ca_b, const int32_t *cb_a,
                                        const int32_t *cb_b, const int32_t *cc_a, const int32_t *cc_b,
@@ -629,42 +657,17 @@ extern "C" int tfhe_amd_gate_batch_dev(TfheAmdContext *c, int gate, int B, int32
     if (!c || B < 0 || !c->key.has_bk || !c->key.ksk) return TFHE_AMD_E_ARG;
     if (B == 0) return TFHE_AMD_OK;
     if (!res_a || !res_b || !ca_a || !ca_b || !cb_a || !cb_b) return TFHE_AMD_E_ARG;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    DeviceScope dev_scope(c->device);
-    HIPCHK(dev_scope.rc);
-    TraceScope trace(c);
-    int rc = tfhe_amd_reserve(c, B);
-    if (rc) return rc;
-    HIPCHK(c->fence.acquire(s));
     if (gate == TFHE_GATE_MUX) {
         if (!cc_a || !cc_b) return TFHE_AMD_E_ARG;
         // boot-gates.cu:407-448: u1 = woKS(-1/8 + a + b), u2 = woKS(-1/8 - a + c),
         // result = KS((0, 1/8) + u1 + u2)
-        BrInput in[2] = {{ca_a, ca_b, cb_a, cb_b, -kMu, 1, 1}, {ca_a, ca_b, cc_a, cc_b, -kMu, -1, 1}};
-        {
-            ProfScope ps(c, s, true);
-            const Guard gd = ctx_guard(c);
-            HIPCHK(run_br(c->key, B, 2, in, kMu, c->u_a, c->u_b, s, &gd));
-        }
-        ProfScope ps(c, s, false);
-        HIPCHK(launch_keyswitch(c->key, B, c->u_a, c->u_b, c->u_a + (size_t)B * kN, c->u_b + B, kMu,
-                                res_a, res_b, s));
-        HIPCHK(c->fence.done(s));
-        return TFHE_AMD_OK;
+        const BrInput in[2] = {{ca_a, ca_b, cb_a, cb_b, -kMu, 1, 1}, {ca_a, ca_b, cc_a, cc_b, -kMu, -1, 1}};
+        return batch_dev(c, stream, B, B, 2, in, kMu, nullptr, nullptr, B, kMu, res_a, res_b);
     }
     BrInput in;
     if (!gate_spec(gate, &in.c, &in.sa, &in.sb)) return TFHE_AMD_E_ARG;
     in.x_a = ca_a; in.x_b = ca_b; in.y_a = cb_a; in.y_b = cb_b;
-    {
-        ProfScope ps(c, s, true);
-        const Guard gd = ctx_guard(c);
-        HIPCHK(run_br(c->key, B, 1, &in, kMu, c->u_a, c->u_b, s, &gd));
-    }
-    ProfScope ps(c, s, false);
-    HIPCHK(launch_keyswitch(c->key, B, c->u_a, c->u_b, nullptr, nullptr, 0, res_a, res_b, s));
-    HIPCHK(c->fence.done(s));
-    return TFHE_AMD_OK;
+    return batch_dev(c, stream, B, B, 1, &in, kMu, nullptr, nullptr, B, 0, res_a, res_b);
 }
 
 extern "C" int tfhe_amd_bootstrap_woks_batch_dev(TfheAmdContext *c, int B, int32_t mu, const int32_t *x_a,
@@ -672,22 +675,8 @@ extern "C" int tfhe_amd_bootstrap_woks_batch_dev(TfheAmdContext *c, int B, int32
     if (!c || B < 0 || !c->key.has_bk) return TFHE_AMD_E_ARG;
     if (B == 0) return TFHE_AMD_OK;
     if (!x_a || !x_b || !u_a || !u_b) return TFHE_AMD_E_ARG;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    DeviceScope dev_scope(c->device);
-    HIPCHK(dev_scope.rc);
-    TraceScope trace(c);
-    int rc = tfhe_amd_reserve(c, B);   // guard flags live in the context's scratch
-    if (rc) return rc;
-    HIPCHK(c->fence.acquire(s));
-    BrInput in{x_a, x_b, nullptr, nullptr, 0, 1, 0};
-    {
-        ProfScope ps(c, s, true);
-        const Guard gd = ctx_guard(c);
-        HIPCHK(run_br(c->key, B, 1, &in, mu, u_a, u_b, s, &gd));
-    }
-    HIPCHK(c->fence.done(s));
-    return TFHE_AMD_OK;
+    const BrInput in{x_a, x_b, nullptr, nullptr, 0, 1, 0};
+    return batch_dev(c, stream, B, B, 1, &in, mu, u_a, u_b);   // (the guard flags live in the context's scratch)
 }
 
 extern "C" int tfhe_amd_bootstrap_batch_dev(TfheAmdContext *c, int B, int32_t mu, const int32_t *x_a,
@@ -695,24 +684,8 @@ extern "C" int tfhe_amd_bootstrap_batch_dev(TfheAmdContext *c, int B, int32_t mu
     if (!c || B < 0 || !c->key.has_bk || !c->key.ksk) return TFHE_AMD_E_ARG;
     if (B == 0) return TFHE_AMD_OK;
     if (!x_a || !x_b || !res_a || !res_b) return TFHE_AMD_E_ARG;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    DeviceScope dev_scope(c->device);
-    HIPCHK(dev_scope.rc);
-    TraceScope trace(c);
-    int rc = tfhe_amd_reserve(c, B);
-    if (rc) return rc;
-    HIPCHK(c->fence.acquire(s));
-    BrInput in{x_a, x_b, nullptr, nullptr, 0, 1, 0};
-    {
-        ProfScope ps(c, s, true);
-        const Guard gd = ctx_guard(c);
-        HIPCHK(run_br(c->key, B, 1, &in, mu, c->u_a, c->u_b, s, &gd));
-    }
-    ProfScope ps(c, s, false);
-    HIPCHK(launch_keyswitch(c->key, B, c->u_a, c->u_b, nullptr, nullptr, 0, res_a, res_b, s));
-    HIPCHK(c->fence.done(s));
-    return TFHE_AMD_OK;
+    const BrInput in{x_a, x_b, nullptr, nullptr, 0, 1, 0};
+    return batch_dev(c, stream, B, B, 1, &in, mu, nullptr, nullptr, B, 0, res_a, res_b);
 }
 
 // ------------------------------------------------------------------ programmable bootstrapping
@@ -755,28 +728,11 @@ static int lut_batch_dev(TfheAmdContext *c, bool ks, int B, int n_lut, const int
     if ((long)B * n_res > 0x3fffffffL) return TFHE_AMD_E_ARG;
     if (B == 0) return TFHE_AMD_OK;
     if (!x_a || !x_b || !out_a || !out_b || (sb && (!y_a || !y_b)) || (sc && (!z_a || !z_b))) return TFHE_AMD_E_ARG;
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    std::lock_guard<std::recursive_mutex> lk(c->mu);
-    DeviceScope dev_scope(c->device);
-    HIPCHK(dev_scope.rc);
-    TraceScope trace(c);
+    const BrInput in{x_a, x_b, sb ? y_a : nullptr, sb ? y_b : nullptr, cst, sa, sb, n_lut, tv, lut_index, log_nu, n_out,
+                     sc ? z_a : nullptr, sc ? z_b : nullptr, sc};
     // guard flags (per ciphertext) and the extracted samples (per output) live in the context's scratch
-    int rc = tfhe_amd_reserve(c, B * n_res);
-    if (rc) return rc;
-    HIPCHK(c->fence.acquire(s));
-    BrInput in{x_a, x_b, sb ? y_a : nullptr, sb ? y_b : nullptr, cst, sa, sb, n_lut, tv, lut_index, log_nu, n_out,
-               sc ? z_a : nullptr, sc ? z_b : nullptr, sc};
-    {
-        ProfScope ps(c, s, true);
-        const Guard gd = ctx_guard(c);
-        HIPCHK(run_br(c->key, B, 1, &in, 0, ks ? c->u_a : out_a, ks ? c->u_b : out_b, s, &gd));
-    }
-    if (ks) {
-        ProfScope ps(c, s, false);
-        HIPCHK(launch_keyswitch(c->key, B * n_res, c->u_a, c->u_b, nullptr, nullptr, 0, out_a, out_b, s));
-    }
-    HIPCHK(c->fence.done(s));
-    return TFHE_AMD_OK;
+    if (ks) return batch_dev(c, stream, B * n_res, B, 1, &in, 0, nullptr, nullptr, B * n_res, 0, out_a, out_b);
+    return batch_dev(c, stream, B * n_res, B, 1, &in, 0, out_a, out_b);
 }
 
 extern "C" int tfhe_amd_bootstrap_lut_many_woks_batch_dev(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,
@@ -1549,7 +1505,7 @@ extern "C" int tfhe_amd_gate_batch_mixed_host(TfheAmdContext *c, int B, const in
         ProfScope ps(c, s, true);
         const Guard gd = ctx_guard(c);
         HIPCHK(launch_blind_rotate_rows(c->key, 1, rows, (const CircRow *)c->mtab, d, d + WA, kMu, c->u_a, c->u_b, s,
-                                        &gd));
+                                        BrMode::Const, &gd));
     }
     {
         ProfScope ps(c, s, false);
@@ -1565,36 +1521,97 @@ extern "C" int tfhe_amd_gate_batch_mixed_host(TfheAmdContext *c, int B, const in
     return TFHE_AMD_OK;
 }
 
-// woKS / bootstrap / KS host versions: same staging scheme (in-place safe)
+// Pinned staging of the staged host paths below.  The caller lists its input arrays and its output
+// arrays (host pointer, 32-bit words; a null pointer is an absent block of no words); the blocks lie
+// back to back, inputs first, at the same offsets in the pinned h_io and the device io.  upload
+// stages every input and issues one copy in; after the device call, download issues one copy out,
+// waits for it and unstages the outputs.  Every input is staged before anything is written back, so
+// outputs may alias inputs.
+namespace {
+struct HostIn {
+    const int32_t *p;
+    size_t words;
+};
+struct HostOut {
+    int32_t *p;
+    size_t words;
+};
+class Staging {
+public:
+    Staging(std::initializer_list<HostIn> in, std::initializer_list<HostOut> out) : in_(in), out_(out) {
+        for (HostIn &b : in_) {
+            if (!b.p) b.words = 0;
+            in_words_ += b.words;
+        }
+        for (HostOut &b : out_) {
+            if (!b.p) b.words = 0;
+            out_words_ += b.words;
+        }
+    }
+    // the capacity (tfhe_amd_reserve) whose io scratch holds every block
+    size_t cap() const { return (in_words_ + out_words_ + io_words(1) - 1) / io_words(1); }
+    // device addresses of input / output block i (null: absent)
+    const int32_t *in(const TfheAmdContext *c, size_t i) const {
+        size_t off = 0;
+        for (size_t k = 0; k < i; ++k) off += in_[k].words;
+        return in_[i].p ? c->io + off : nullptr;
+    }
+    int32_t *out(const TfheAmdContext *c, size_t i) const {
+        size_t off = in_words_;
+        for (size_t k = 0; k < i; ++k) off += out_[k].words;
+        return out_[i].p ? c->io + off : nullptr;
+    }
+    int upload(TfheAmdContext *c) const {
+        size_t off = 0;
+        for (const HostIn &b : in_) {
+            if (b.words) memcpy(c->h_io + off, b.p, b.words * 4);
+            off += b.words;
+        }
+        HIPCHK(hipMemcpyAsync(c->io, c->h_io, in_words_ * 4, hipMemcpyHostToDevice, c->stream));
+        return TFHE_AMD_OK;
+    }
+    int download(TfheAmdContext *c) const {
+        size_t off = in_words_;
+        HIPCHK(hipMemcpyAsync(c->h_io + off, c->io + off, out_words_ * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        for (const HostOut &b : out_) {
+            if (b.words) memcpy(b.p, c->h_io + off, b.words * 4);
+            off += b.words;
+        }
+        return TFHE_AMD_OK;
+    }
+
+private:
+    std::vector<HostIn> in_;
+    std::vector<HostOut> out_;
+    size_t in_words_ = 0, out_words_ = 0;
+};
+}  // namespace
+
+// woKS / bootstrap / KS host versions
 enum { OP_WOKS, OP_BOOT, OP_KS };
 static int single_input_host(TfheAmdContext *c, int op, int B, int32_t mu, const int32_t *in_a,
                              const int32_t *in_b, int32_t *out_a, int32_t *out_b) {
     if (!c || B < 0) return TFHE_AMD_E_ARG;
     if (B == 0) return TFHE_AMD_OK;
     if (!in_a || !in_b || !out_a || !out_b) return TFHE_AMD_E_ARG;
+    const int din = op == OP_KS ? kN : kn, dout = op == OP_WOKS ? kN : kn;
+    // [in_a | in_b | out_a | out_b]: B * (din + dout + 2) <= 1526 B words, within B slots' 2004 B
+    const Staging st({{in_a, (size_t)B * din}, {in_b, (size_t)B}}, {{out_a, (size_t)B * dout}, {out_b, (size_t)B}});
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     DeviceScope dev_scope(c->device);
     HIPCHK(dev_scope.rc);
     TraceScope trace(c);
     int rc = tfhe_amd_reserve(c, B);
     if (rc) return rc;
-    const int din = op == OP_KS ? kN : kn, dout = op == OP_WOKS ? kN : kn;
-    const size_t Ai = (size_t)B * din, Ao = (size_t)B * dout;
-    int32_t *h = c->h_io, *d = c->io;
-    // [in_a | in_b | out_a | out_b]  (<= B * (1025 + 1025) words <= 4 * cap * 501)
-    memcpy(h, in_a, Ai * 4);
-    memcpy(h + Ai, in_b, (size_t)B * 4);
-    HIPCHK(hipMemcpyAsync(d, h, (Ai + B) * 4, hipMemcpyHostToDevice, c->stream));
-    int32_t *oa = d + Ai + B, *ob = oa + Ao;
-    if (op == OP_WOKS) rc = tfhe_amd_bootstrap_woks_batch_dev(c, B, mu, d, d + Ai, oa, ob, c->stream);
-    else if (op == OP_BOOT) rc = tfhe_amd_bootstrap_batch_dev(c, B, mu, d, d + Ai, oa, ob, c->stream);
-    else rc = tfhe_amd_keyswitch_batch_dev(c, B, d, d + Ai, oa, ob, c->stream);
+    if ((rc = st.upload(c))) return rc;
+    const int32_t *d_a = st.in(c, 0), *d_b = st.in(c, 1);
+    int32_t *oa = st.out(c, 0), *ob = st.out(c, 1);
+    if (op == OP_WOKS) rc = tfhe_amd_bootstrap_woks_batch_dev(c, B, mu, d_a, d_b, oa, ob, c->stream);
+    else if (op == OP_BOOT) rc = tfhe_amd_bootstrap_batch_dev(c, B, mu, d_a, d_b, oa, ob, c->stream);
+    else rc = tfhe_amd_keyswitch_batch_dev(c, B, d_a, d_b, oa, ob, c->stream);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h + Ai + B, oa, (Ao + B) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(out_a, h + Ai + B, Ao * 4);
-    memcpy(out_b, h + Ai + B + Ao, (size_t)B * 4);
-    return TFHE_AMD_OK;
+    return st.download(c);
 }
 
 extern "C" int tfhe_amd_bootstrap_woks_batch_host(TfheAmdContext *c, int B, int32_t mu, const int32_t *x_a,
@@ -1611,7 +1628,7 @@ extern "C" int tfhe_amd_keyswitch_batch_host(TfheAmdContext *c, int B, const int
 }
 
 // programmable bootstrap, host arrays: the staged path of single_input_host with the tables
-// (n_lut x 4 KB) and the table indices uploaded beside the inputs (in-place safe)
+// (n_lut x 4 KB) and the table indices uploaded beside the inputs
 static int lut_batch_host(TfheAmdContext *c, bool ks, int B, int n_lut, const int32_t *tv, const int32_t *lut_index,
                           int32_t cst, int32_t sa, const int32_t *x_a, const int32_t *x_b, int32_t sb,
                           const int32_t *y_a, const int32_t *y_b, int32_t *out_a, int32_t *out_b, int log_nu = 0,
@@ -1624,71 +1641,46 @@ static int lut_batch_host(TfheAmdContext *c, bool ks, int B, int n_lut, const in
             if (lut_index[i] < 0 || lut_index[i] >= n_lut) return TFHE_AMD_E_ARG;
     if (B == 0) return TFHE_AMD_OK;
     if (!x_a || !x_b || !out_a || !out_b || (sb && (!y_a || !y_b))) return TFHE_AMD_E_ARG;
-    // [x_a | x_b | y_a | y_b | tables | indices | out_a | out_b] in the io scratch (4 cap x 501 words)
-    const int dout = ks ? kn : kN;
-    const size_t Ai = (size_t)B * kn, Ao = n_res * B * dout, Bo = n_res * B, Tw = (size_t)n_lut * kN;
-    const size_t o_y = Ai + B, o_tv = o_y + (sb ? Ai + B : 0), o_ix = o_tv + Tw, o_out = o_ix + (lut_index ? B : 0);
-    const size_t need = o_out + Ao + Bo, cap = (need + io_words(1) - 1) / io_words(1);
-    if (cap > ((size_t)1 << 24)) return TFHE_AMD_E_ARG;
+    // [x_a | x_b | y_a | y_b | tables | indices | out_a | out_b]
+    const size_t Ai = (size_t)B * kn, Bo = n_res * B, Ao = Bo * (ks ? kn : kN);
+    const Staging st({{x_a, Ai}, {x_b, (size_t)B}, {sb ? y_a : nullptr, Ai}, {sb ? y_b : nullptr, (size_t)B},
+                      {tv, (size_t)n_lut * kN}, {lut_index, (size_t)B}},
+                     {{out_a, Ao}, {out_b, Bo}});
+    if (st.cap() > ((size_t)1 << 24)) return TFHE_AMD_E_ARG;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     DeviceScope dev_scope(c->device);
     HIPCHK(dev_scope.rc);
     TraceScope trace(c);
-    int rc = tfhe_amd_reserve(c, std::max((int)Bo, (int)cap));
+    int rc = tfhe_amd_reserve(c, std::max((int)Bo, (int)st.cap()));
     if (rc) return rc;
-    int32_t *h = c->h_io, *d = c->io;
-    memcpy(h, x_a, Ai * 4);
-    memcpy(h + Ai, x_b, (size_t)B * 4);
-    if (sb) {
-        memcpy(h + o_y, y_a, Ai * 4);
-        memcpy(h + o_y + Ai, y_b, (size_t)B * 4);
-    }
-    memcpy(h + o_tv, tv, Tw * 4);
-    if (lut_index) memcpy(h + o_ix, lut_index, (size_t)B * 4);
-    HIPCHK(hipMemcpyAsync(d, h, o_out * 4, hipMemcpyHostToDevice, c->stream));
-    int32_t *oa = d + o_out, *ob = oa + Ao;
-    rc = lut_batch_dev(c, ks, B, n_lut, d + o_tv, lut_index ? d + o_ix : nullptr, cst, sa, d, d + Ai, sb,
-                       sb ? d + o_y : nullptr, sb ? d + o_y + Ai : nullptr, oa, ob, c->stream, log_nu, n_out);
+    if ((rc = st.upload(c))) return rc;
+    rc = lut_batch_dev(c, ks, B, n_lut, st.in(c, 4), st.in(c, 5), cst, sa, st.in(c, 0), st.in(c, 1), sb, st.in(c, 2),
+                       st.in(c, 3), st.out(c, 0), st.out(c, 1), c->stream, log_nu, n_out);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h + o_out, oa, (Ao + Bo) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(out_a, h + o_out, Ao * 4);
-    memcpy(out_b, h + o_out + Ao, Bo * 4);
-    return TFHE_AMD_OK;
+    return st.download(c);
 }
 
-// the staged path: [a | b | c | res] in the io scratch (5 B x 501 words; res may alias an input)
+// the staged path: [a | b | c | res] in the io scratch (5 B x 501 words)
 extern "C" int tfhe_amd_full_add_batch_host(TfheAmdContext *c, int B, int enc_sum, int enc_carry, const int32_t *a_a,
                                             const int32_t *a_b, const int32_t *b_a, const int32_t *b_b,
                                             const int32_t *c_a, const int32_t *c_b, int32_t *res_a, int32_t *res_b) {
     if (!full_add_args_ok(c, B, enc_sum, enc_carry, c_a, c_b)) return TFHE_AMD_E_ARG;
     if (B == 0) return TFHE_AMD_OK;
     if (!a_a || !a_b || !b_a || !b_b || !res_a || !res_b) return TFHE_AMD_E_ARG;
-    const size_t Ai = (size_t)B * kn, In = Ai + B, n_in = c_a ? 3 : 2, o_out = n_in * In;
-    const size_t need = o_out + 2 * In, cap = (need + io_words(1) - 1) / io_words(1);
-    if (cap > ((size_t)1 << 24)) return TFHE_AMD_E_ARG;
+    const size_t Ai = (size_t)B * kn, Bw = (size_t)B;
+    const Staging st({{a_a, Ai}, {a_b, Bw}, {b_a, Ai}, {b_b, Bw}, {c_a, Ai}, {c_b, Bw}}, {{res_a, 2 * Ai}, {res_b, 2 * Bw}});
+    if (st.cap() > ((size_t)1 << 24)) return TFHE_AMD_E_ARG;
     std::lock_guard<std::recursive_mutex> lk(c->mu);
     DeviceScope dev_scope(c->device);
     HIPCHK(dev_scope.rc);
     TraceScope trace(c);
-    int rc = tfhe_amd_reserve(c, std::max(2 * B, (int)cap));   // 2 B: the device form's extracted samples
+    int rc = tfhe_amd_reserve(c, std::max(2 * B, (int)st.cap()));   // 2 B: the device form's extracted samples
     if (rc) return rc;
-    int32_t *h = c->h_io, *d = c->io;
-    const int32_t *src[3][2] = {{a_a, a_b}, {b_a, b_b}, {c_a, c_b}};
-    for (size_t t = 0; t < n_in; ++t) {
-        memcpy(h + t * In, src[t][0], Ai * 4);
-        memcpy(h + t * In + Ai, src[t][1], (size_t)B * 4);
-    }
-    HIPCHK(hipMemcpyAsync(d, h, o_out * 4, hipMemcpyHostToDevice, c->stream));
-    int32_t *oa = d + o_out, *ob = oa + 2 * Ai;
-    rc = tfhe_amd_full_add_batch_dev(c, B, enc_sum, enc_carry, d, d + Ai, d + In, d + In + Ai, c_a ? d + 2 * In : nullptr,
-                                     c_a ? d + 2 * In + Ai : nullptr, oa, ob, c->stream);
+    if ((rc = st.upload(c))) return rc;
+    rc = tfhe_amd_full_add_batch_dev(c, B, enc_sum, enc_carry, st.in(c, 0), st.in(c, 1), st.in(c, 2), st.in(c, 3),
+                                     st.in(c, 4), st.in(c, 5), st.out(c, 0), st.out(c, 1), c->stream);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(h + o_out, oa, 2 * In * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    memcpy(res_a, h + o_out, 2 * Ai * 4);
-    memcpy(res_b, h + o_out + 2 * Ai, (size_t)2 * B * 4);
-    return TFHE_AMD_OK;
+    return st.download(c);
 }
 
 extern "C" int tfhe_amd_bootstrap_lut_many_woks_batch_host(TfheAmdContext *c, int B, int n_lut, const int32_t *tv,

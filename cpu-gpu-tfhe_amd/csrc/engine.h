@@ -10,9 +10,9 @@ namespace tfhe_amd {
 // Key material of one cloud key resident on one GPU.
 struct DeviceKey {
     int device = -1;
-    uint32_t *bk_ntt = nullptr;   // v1: [kn][2 primes][kKpl][2][kN], Montgomery form, 1/N folded
-    uint32_t *bk_v2 = nullptr;    // v2: [kn][2 primes][2 c][kKpl][4 v][64 L][4 e] (same values)
-    uint2 *tw2 = nullptr;         // v2 twiddles: uniform fwd/inv [2][16] x2, streams [2][27][64], [2][18][64]
+    uint32_t *bk_ntt = nullptr;   // upload only (freed once repacked): [kn][2 primes][kKpl][2][kN], Montgomery form, 1/N folded
+    uint32_t *bk_v2 = nullptr;    // the exact (v4) kernels' key: [kn][2 primes][2 c][kKpl][4 v][64 L][4 e] (same values)
+    uint2 *tw2 = nullptr;         // v4 forward twiddles: uniform fwd/inv [2][16] x2, streams [2][27][64], [2][18][64]
     uint2 *tw4 = nullptr;         // v4 inverse-CT twiddles: uniform [2][16], streams [2][27][64], post-twist [2][16][64]
     double2 *bk_fft = nullptr;    // v6: [kn][4 rows][2 c][8 r][64 L] FFT-domain key / 512 (slot 8 L + r)
     double2 *tw6 = nullptr;       // v6 twiddles: forward [4] + [4][64] x 2, inverse [4][64] x 2, post-twist [8][64]
@@ -40,6 +40,7 @@ constexpr int kTw6Words = 4 + 4 * 4 * 64 + 8 * 64 + 2 * 64;   // fft_wave.h tabl
 // coefficients f = 0 .. n_out - 1 of the rotated accumulator; output f of ciphertext g goes to u
 // sample f B + g, so u holds n_out B samples.  n_out = 0: the single-table launch above.
 // With tv set the input may have a third term: x = (0, c) + sa * X + sb * Y + sc * Z.
+// Which of the three forms a launch takes is its BrMode (br_mode below), derived once per launch.
 struct BrInput {
     const int32_t *x_a, *x_b;
     const int32_t *y_a, *y_b;
@@ -59,8 +60,8 @@ struct BrInput {
 // lut: 0 = the constant test vector (mu, ..., mu); otherwise the row's test vector of kN words
 // starts `lut` 32-bit words after the row's own record, in the same device allocation (the level
 // tables and the circuit's LUT tables are uploaded as one block, so the offset is the same on every
-// device).  Only launches whose Guard says lut_rows read it.
-// many (launches whose Guard says many_rows): 0 = one output; otherwise log_nu | n_out << 8 of a
+// device).  Only launches of mode Lut or Many read it.
+// many (launches of mode Many): 0 = one output; otherwise log_nu | n_out << 8 of a
 // many-LUT row.  Output 0 of row r goes to u row r like every row's; outputs
 // f >= 1 go to the u rows urow + f - 1, which lie behind the level's nrows rows.
 struct CircRow {
@@ -127,29 +128,46 @@ struct StreamFence {
 // an exact-NTT (v4) launch in guard mode then recomputes every ciphertext whose flag reaches the
 // threshold (1/8 by default) and exits at once for all others.  stats[0] counts the recomputed
 // ciphertexts, stats[1] holds the largest high word seen (tfhe_amd_guard_stats).
-// lut_rows (rows launches only): some row of the level carries a test vector (CircRow.lut), so
-// the rows launchers take the kernels' LUT instantiation; it rides here because the row records
-// themselves are in device memory.  With flags null it is the only thing the struct says.
-// many_rows (rows launches only, implies lut_rows): some row is a many-LUT row (CircRow.many), so
-// the launchers take the many-LUT instantiation.  The flags stay per row x instance.
 struct Guard {
     uint32_t *flags = nullptr;
     uint32_t *stats = nullptr;
-    bool lut_rows = false;
-    bool many_rows = false;
 };
 uint32_t guard_threshold_hi();
+
+// The form of a blind-rotation launch, i.e. which instantiation of the kernels it takes: the
+// constant test vector (mu, ..., mu), caller-supplied test vectors (programmable bootstrap), or
+// test vectors with several extracted outputs (many-LUT; implies Lut).  A rows launch is told its
+// mode (the row records are in device memory): Lut if some row of the level carries a test vector
+// (CircRow.lut), Many if some row is a many-LUT row (CircRow.many).
+enum class BrMode { Const, Lut, Many };
+// The mode of a launch over in[0 .. halves), or hipErrorInvalidValue for an inconsistent one.
+inline hipError_t br_mode(const BrInput *in, int halves, BrMode *mode) {
+    const BrInput &in1 = halves > 1 ? in[1] : in[0];
+    // programmable bootstrap: every half carries its tables (n_lut >= 1), or none does
+    const bool lut = in[0].tv != nullptr;
+    if (lut != (in1.tv != nullptr) || (lut && (in[0].n_lut <= 0 || in1.n_lut <= 0))) return hipErrorInvalidValue;
+    // many-LUT: one half, tables, log_nu in [0, 4], n_out in [1, 2^log_nu]
+    const bool many = in[0].n_out != 0;
+    if (many && (!lut || halves != 1 || in[0].log_nu < 0 || in[0].log_nu > 4 || in[0].n_out < 1 ||
+                 in[0].n_out > (1 << in[0].log_nu)))
+        return hipErrorInvalidValue;
+    // third input: only the LUT instantiations read it
+    for (const BrInput *h : {&in[0], &in1})
+        if (h->sc && (!lut || !h->z_a || !h->z_b)) return hipErrorInvalidValue;
+    *mode = many ? BrMode::Many : lut ? BrMode::Lut : BrMode::Const;
+    return hipSuccess;
+}
 
 // BK conversion (coefficient -> NTT domain) on the device; d_bk_coef = [kn][4][2][kN]
 hipError_t launch_bk_to_ntt(const int32_t *d_bk_coef, uint32_t *d_bk_ntt, const NttTables *d_tab,
                             hipStream_t s);
-// Blind rotation + sample extraction for `halves` x B ciphertexts: ciphertext g of half h
-// reads in[h] at index g and writes u[h*B + g] (u_a row stride kN).
 // the NTT-domain key layouts and their twiddle streams (ntt_key.hip), used by the v4 kernels
 void build_v2_twiddles(const NttTables &t, uint2 *tu_f, uint2 *tu_i, uint2 *ts_f, uint2 *ts_i);
 hipError_t launch_bk_v1_to_v2(const uint32_t *d_v1, uint32_t *d_v2, hipStream_t s);
 // v4 (v2 layout, inverse CT + lazy CRT + periodic accumulator), blind_rotate_v4.hip
 void build_v4_twiddles(const NttTables &t, uint2 *tu_i, uint2 *ts_i, uint2 *tpost);
+// Blind rotation + sample extraction for `halves` x B ciphertexts (v4 and v6 alike): ciphertext g
+// of half h reads in[h] at index g and writes u[h*B + g] (u_a row stride kN).
 // guard != null: guard mode (recompute only the ciphertexts whose v6 flag reached the threshold)
 hipError_t launch_blind_rotate_v4(const DeviceKey &key, int B, int halves, const BrInput *in, int32_t mu,
                                   int32_t *u_a, int32_t *u_b, hipStream_t s, const Guard *guard = nullptr);
@@ -161,7 +179,7 @@ hipError_t launch_external_product_v4(const DeviceKey &key, int B, const int32_t
 // circuit level (v4 kernel): B instances x nrows rows, wires [W][B] ciphertexts, u slots r B + k
 hipError_t launch_blind_rotate_v4_rows(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
-                                       const Guard *guard = nullptr);
+                                       BrMode mode, const Guard *guard = nullptr);
 // v6 (fp64 FFT external product, the reference's arithmetic), blind_rotate_v6.hip
 void build_v6_twiddles(double2 *tw);
 hipError_t launch_bk_to_fft(const int32_t *d_bk_coef, double2 *d_bkf, const double2 *d_tw, hipStream_t s);
@@ -170,7 +188,7 @@ hipError_t launch_blind_rotate_v6(const DeviceKey &key, int B, int halves, const
                                   int32_t *u_a, int32_t *u_b, hipStream_t s, const Guard *guard = nullptr);
 hipError_t launch_blind_rotate_v6_rows(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
-                                       const Guard *guard = nullptr);
+                                       BrMode mode, const Guard *guard = nullptr);
 hipError_t launch_blind_rotate_v6_debug(const DeviceKey &key, int B, int iters, int32_t *acc,
                                         const int32_t *bara, hipStream_t s);
 // which blind-rotation kernel runs: 0 = default (v6), 4 = exact NTT (tfhe_amd_select_kernel)
@@ -179,14 +197,13 @@ int br_version();
 // the C ABI collects the names of its launches into its context (tfhe_amd_last_kernels), so a
 // smoke or bench run can say which kernels produced the results it checked.
 void trace_kernel(const char *name);
-// circuit level blind rotation with the selected kernel (rows variants of v4 / v5 / v6); the
-// default fp64 kernel runs guarded (flags: 2 words per row x instance); guard->lut_rows picks the
-// LUT instantiations (in exact mode too, where the flags are not used)
+// circuit level blind rotation with the selected kernel (the rows variant of v6 or v4); the default
+// fp64 kernel runs guarded (flags: 2 words per row x instance), the exact one does not use the guard
 hipError_t launch_blind_rotate_rows(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                     const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
-                                    const Guard *guard);
+                                    BrMode mode, const Guard *guard);
 
-// which key-switch kernel runs: 1..4 (env TFHE_AMD_KS)
+// which key-switch kernel the larger batches take: 5 (int8 MFMA), or 4 with TFHE_AMD_KS5=0
 int ks_version();
 size_t ksk_v4_words();
 size_t ksk_v5_words();

@@ -413,13 +413,5 @@ __device__ __forceinline__ Tw4 tw7_invA(const double2 *t, int L) {
     return Tw4{ld(p), ld(p + 64), ld(p + 128), ld(p + 192)};
 }
 
-// The linear combination x = (0, c) + sa X + sb Y + sc Z that feeds one blind rotation (gate
-// prologues boot-gates.cu:98-448; a circuit row adds a third input for MAJ / XOR3); y / z may
-// be null.
-struct RowTerms6 {
-    int32_t c, sa, sb, sc;
-    const int32_t *xa, *xb, *ya, *yb, *za, *zb;
-};
-
 }  // namespace
 }  // namespace tfhe_amd

@@ -634,7 +634,8 @@ class Context:
     # ---- programmable bootstrapping (tfhe_amd_bootstrap_lut_*): tv = test vectors [n_lut][1024] (or
     # one [1024]), lut_index [B] picks each ciphertext's table (None: table 0); the blind-rotation
     # input is (0, c) + sa X + sb Y
-    def _lut_host(self, ks, tv, x_a, x_b, lut_index, c, sa, sb, y_a, y_b):
+    # log_nu / n_out given: the many-LUT entry points, outputs function-major ([n_out][B][...])
+    def _lut_host(self, ks, tv, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, log_nu=None, n_out=None):
         tv = i32(tv).reshape(-1, N)
         x_a = i32(x_a); B = x_a.shape[0]
         idx = None if lut_index is None else i32(lut_index)
@@ -642,11 +643,14 @@ class Context:
             raise TfheAmdError(f"lut_index: need one table index per ciphertext ({B}), got {idx.shape}")
         if int(sb) != 0 and (y_a is None or y_b is None):
             raise TfheAmdError("sb != 0 needs y_a, y_b")
-        r_a = np.zeros((B, n_lwe if ks else N), np.int32); r_b = np.zeros(B, np.int32)
-        fn = lib.tfhe_amd_bootstrap_lut_batch_host if ks else lib.tfhe_amd_bootstrap_lut_woks_batch_host
-        _check(fn(self.h, B, tv.shape[0], _p(tv), _p(idx), int(c), int(sa), _p(x_a), _p(i32(x_b)), int(sb),
-                  _p(None if y_a is None else i32(y_a)), _p(None if y_b is None else i32(y_b)), _p(r_a), _p(r_b)),
-               "bootstrap_lut_batch_host" if ks else "bootstrap_lut_woks_batch_host")
+        many = n_out is not None
+        lead = (max(int(n_out), 1),) if many else ()
+        r_a = np.zeros(lead + (B, n_lwe if ks else N), np.int32); r_b = np.zeros(lead + (B,), np.int32)
+        name = "bootstrap_lut" + ("_many" if many else "") + ("" if ks else "_woks") + "_batch_host"
+        _check(getattr(lib, "tfhe_amd_" + name)(
+            self.h, B, tv.shape[0], _p(tv), _p(idx), *((int(log_nu), int(n_out)) if many else ()), int(c), int(sa),
+            _p(x_a), _p(i32(x_b)), int(sb), _p(None if y_a is None else i32(y_a)),
+            _p(None if y_b is None else i32(y_b)), _p(r_a), _p(r_b)), name)
         return r_a, r_b
 
     def lut_woks_host(self, tv, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None):
@@ -657,12 +661,15 @@ class Context:
         """tfhe_amd_bootstrap_lut_batch_host -> the key-switched results (r_a [B][500], r_b [B])"""
         return self._lut_host(True, tv, x_a, x_b, lut_index, c, sa, sb, y_a, y_b)
 
-    def _lut_dev(self, ks, tv, out_a, out_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream):
+    def _lut_dev(self, ks, tv, out_a, out_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream, log_nu=None,
+                 n_out=None):
         B = x_a.shape[0]
         if tv is None or tv.dim() != 2 or tv.shape[0] < 1:
             raise TfheAmdError("tv: need a GPU tensor [n_lut][1024]")
         n_lut = tv.shape[0]
-        named = [("tv", tv, (n_lut, N)), ("out_a", out_a, (B, n_lwe if ks else N)), ("out_b", out_b, (B,)),
+        many = n_out is not None
+        lead = (max(int(n_out), 1),) if many else ()
+        named = [("tv", tv, (n_lut, N)), ("out_a", out_a, lead + (B, n_lwe if ks else N)), ("out_b", out_b, lead + (B,)),
                  ("x_a", x_a, (B, n_lwe)), ("x_b", x_b, (B,))]
         if lut_index is not None:
             named.append(("lut_index", lut_index, (B,)))
@@ -671,10 +678,11 @@ class Context:
         for name, t, shape in named:
             self._dev_check(t, shape, name)
         ptr = (lambda t: None if t is None else t.data_ptr())
-        fn = lib.tfhe_amd_bootstrap_lut_batch_dev if ks else lib.tfhe_amd_bootstrap_lut_woks_batch_dev
-        _check(fn(self.h, B, n_lut, ptr(tv), ptr(lut_index), int(c), int(sa), ptr(x_a), ptr(x_b), int(sb),
-                  ptr(y_a) if int(sb) else None, ptr(y_b) if int(sb) else None, ptr(out_a), ptr(out_b), stream),
-               "bootstrap_lut_batch_dev" if ks else "bootstrap_lut_woks_batch_dev")
+        name = "bootstrap_lut" + ("_many" if many else "") + ("" if ks else "_woks") + "_batch_dev"
+        _check(getattr(lib, "tfhe_amd_" + name)(
+            self.h, B, n_lut, ptr(tv), ptr(lut_index), *((int(log_nu), int(n_out)) if many else ()), int(c), int(sa),
+            ptr(x_a), ptr(x_b), int(sb), ptr(y_a) if int(sb) else None, ptr(y_b) if int(sb) else None, ptr(out_a),
+            ptr(out_b), stream), name)
 
     def lut_woks_dev(self, tv, u_a, u_b, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None, stream=None):
         """tfhe_amd_bootstrap_lut_woks_batch_dev on torch tensors (as gate_dev); a lut_index entry
@@ -689,63 +697,25 @@ class Context:
     # ---- many-LUT bootstrapping (tfhe_amd_bootstrap_lut_many_*): as the lut_* methods, with the
     # modulus switch to a multiple of 2^log_nu and n_out <= 2^log_nu outputs per ciphertext,
     # function-major ([n_out][B][...])
-    def _lut_many_host(self, ks, tv, log_nu, n_out, x_a, x_b, lut_index, c, sa, sb, y_a, y_b):
-        tv = i32(tv).reshape(-1, N)
-        x_a = i32(x_a); B = x_a.shape[0]
-        idx = None if lut_index is None else i32(lut_index)
-        if idx is not None and idx.shape != (B,):
-            raise TfheAmdError(f"lut_index: need one table index per ciphertext ({B}), got {idx.shape}")
-        if int(sb) != 0 and (y_a is None or y_b is None):
-            raise TfheAmdError("sb != 0 needs y_a, y_b")
-        n = max(int(n_out), 1)
-        r_a = np.zeros((n, B, n_lwe if ks else N), np.int32); r_b = np.zeros((n, B), np.int32)
-        fn = lib.tfhe_amd_bootstrap_lut_many_batch_host if ks else lib.tfhe_amd_bootstrap_lut_many_woks_batch_host
-        _check(fn(self.h, B, tv.shape[0], _p(tv), _p(idx), int(log_nu), int(n_out), int(c), int(sa), _p(x_a),
-                  _p(i32(x_b)), int(sb), _p(None if y_a is None else i32(y_a)),
-                  _p(None if y_b is None else i32(y_b)), _p(r_a), _p(r_b)),
-               "bootstrap_lut_many_batch_host" if ks else "bootstrap_lut_many_woks_batch_host")
-        return r_a, r_b
-
     def lut_many_woks_host(self, tv, log_nu, n_out, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None):
         """tfhe_amd_bootstrap_lut_many_woks_batch_host -> (u_a [n_out][B][1024], u_b [n_out][B])"""
-        return self._lut_many_host(False, tv, log_nu, n_out, x_a, x_b, lut_index, c, sa, sb, y_a, y_b)
+        return self._lut_host(False, tv, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, log_nu, n_out)
 
     def lut_many_bootstrap_host(self, tv, log_nu, n_out, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None,
                                 y_b=None):
         """tfhe_amd_bootstrap_lut_many_batch_host -> (r_a [n_out][B][500], r_b [n_out][B])"""
-        return self._lut_many_host(True, tv, log_nu, n_out, x_a, x_b, lut_index, c, sa, sb, y_a, y_b)
-
-    def _lut_many_dev(self, ks, tv, log_nu, n_out, out_a, out_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream):
-        B = x_a.shape[0]
-        if tv is None or tv.dim() != 2 or tv.shape[0] < 1:
-            raise TfheAmdError("tv: need a GPU tensor [n_lut][1024]")
-        n_lut = tv.shape[0]
-        n = max(int(n_out), 1)
-        named = [("tv", tv, (n_lut, N)), ("out_a", out_a, (n, B, n_lwe if ks else N)), ("out_b", out_b, (n, B)),
-                 ("x_a", x_a, (B, n_lwe)), ("x_b", x_b, (B,))]
-        if lut_index is not None:
-            named.append(("lut_index", lut_index, (B,)))
-        if int(sb) != 0:
-            named += [("y_a", y_a, (B, n_lwe)), ("y_b", y_b, (B,))]
-        for name, t, shape in named:
-            self._dev_check(t, shape, name)
-        ptr = (lambda t: None if t is None else t.data_ptr())
-        fn = lib.tfhe_amd_bootstrap_lut_many_batch_dev if ks else lib.tfhe_amd_bootstrap_lut_many_woks_batch_dev
-        _check(fn(self.h, B, n_lut, ptr(tv), ptr(lut_index), int(log_nu), int(n_out), int(c), int(sa), ptr(x_a),
-                  ptr(x_b), int(sb), ptr(y_a) if int(sb) else None, ptr(y_b) if int(sb) else None, ptr(out_a),
-                  ptr(out_b), stream),
-               "bootstrap_lut_many_batch_dev" if ks else "bootstrap_lut_many_woks_batch_dev")
+        return self._lut_host(True, tv, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, log_nu, n_out)
 
     def lut_many_woks_dev(self, tv, log_nu, n_out, u_a, u_b, x_a, x_b, lut_index=None, c=0, sa=1, sb=0, y_a=None,
                           y_b=None, stream=None):
         """tfhe_amd_bootstrap_lut_many_woks_batch_dev on torch tensors: u_a [n_out][B][1024], u_b [n_out][B]"""
-        self._lut_many_dev(False, tv, log_nu, n_out, u_a, u_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream)
+        self._lut_dev(False, tv, u_a, u_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream, log_nu, n_out)
 
     def lut_many_bootstrap_dev(self, tv, log_nu, n_out, res_a, res_b, x_a, x_b, lut_index=None, c=0, sa=1, sb=0,
                                y_a=None, y_b=None, stream=None):
         """tfhe_amd_bootstrap_lut_many_batch_dev on torch tensors: res_a [n_out][B][500], res_b [n_out][B];
         res may overlap x"""
-        self._lut_many_dev(True, tv, log_nu, n_out, res_a, res_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream)
+        self._lut_dev(True, tv, res_a, res_b, x_a, x_b, lut_index, c, sa, sb, y_a, y_b, stream, log_nu, n_out)
 
     # ---- one-rotation full adders (tfhe_amd_full_add_batch_*): a, b, c = (a [B][500], b [B]) of
     # half-torus bits, c = None: half adders; results [2][B][...]: the sum bits, then the carries

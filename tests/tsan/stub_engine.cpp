@@ -353,7 +353,7 @@ extern "C" int tfhe_amd_circuit_run_dev(TfheAmdContext *c, TfheAmdCircuit *circ,
 namespace tfhe_amd {
 hipError_t launch_blind_rotate_rows(const DeviceKey &, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                     const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t,
-                                    const Guard *) {
+                                    BrMode, const Guard *) {
     for (int r = 0; r < nrows; ++r)
         for (int k = 0; k < B; ++k) {
             const CircRow &w = rows[r];

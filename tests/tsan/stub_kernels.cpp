@@ -126,13 +126,13 @@ static hipError_t br_rows(int B, int nrows, const CircRow *rows, const int32_t *
 }
 hipError_t launch_blind_rotate_v4_rows(const DeviceKey &, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
-                                       const Guard *guard) {
+                                       BrMode, const Guard *guard) {
     if (guard) return hipSuccess;
     return br_rows(B, nrows, rows, wa, wb, mu, u_a, u_b, s, nullptr);
 }
 hipError_t launch_blind_rotate_v6_rows(const DeviceKey &, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
-                                       const Guard *guard) {
+                                       BrMode, const Guard *guard) {
     trace_kernel("stub_blind_rotate_rows");
     return br_rows(B, nrows, rows, wa, wb, mu, u_a, u_b, s, guard);
 }
