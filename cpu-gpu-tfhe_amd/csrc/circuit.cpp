@@ -295,6 +295,9 @@ int compile(TfheAmdCircuit *C) {
         CircRow &r = C->rows[i];
         if (r.lut) r.lut = (int32_t)(head + (size_t)(r.lut - 1) * kN - i * (sizeof(CircRow) / 4));
     }
+    // the device tables of an earlier schedule: dropped with it, whichever call compiled (a circuit
+    // that grew after a run and was then asked for its info would otherwise run on the old block)
+    C->states.clear();
     C->compiled = true;
     return TFHE_AMD_OK;
 }
@@ -554,8 +557,7 @@ int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int de
         std::lock_guard<std::mutex> lk(c->mu);
         if (!c->compiled) {
             const int rc = compile(c);
-            if (rc != TFHE_AMD_OK) return rc;
-            c->states.clear();   // tables of an earlier schedule
+            if (rc != TFHE_AMD_OK) return rc;   // (compile drops the states of the earlier schedule)
         }
         auto &slot = c->states[ctx_uid];
         if (!slot) slot.reset(new CircuitDevState());
