@@ -297,6 +297,93 @@ __global__ __launch_bounds__(kV4Threads, 2) void k_external_product_v4(V4Args g,
     for (int j = tid; j < 2 * kN; j += kV4Threads) accg[j] = (int32_t)sh.E[j >> kLogN][j & (kN - 1)];
 }
 
+// ---- leveled mode on caller-supplied TGSW samples: g.bk points at an imported
+// set (engine.h TgswLookup / TgswCmux), everything else in g is the context's.
+
+// A selector index read from device memory, the same word for the whole workgroup.
+__device__ __forceinline__ int tgsw_sel(const int32_t *p) { return __builtin_amdgcn_readfirstlane(*p); }
+
+// Table lookup: one workgroup per query q.  ACC = table t (trivial sample (0, tab) for tab_rows = 1),
+// then d_h CMux steps on the query's selectors: step i rotates by X^{-2^(i + log_stride)} when the
+// selector encrypts 1, so that coefficient f of the result is tab[(addr << log_stride) + f]; the
+// extraction is the many-LUT epilogue's (br_v4_body), output f of query q to u sample f B + q.
+// A selector outside [0, count) skips its step (uniform) and never forms an address.
+__global__ __launch_bounds__(kV4Threads, 2) void k_tgsw_lookup_v4(V4Args g, TgswLookup a,
+                                                                   int32_t *__restrict__ u_a,
+                                                                   int32_t *__restrict__ u_b) {
+    __shared__ V4Shared sh;
+    const int tid = threadIdx.x;
+    const int s = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int L = tid & 63;
+    const int q = blockIdx.x;
+    const int32_t *src;
+    int rows = a.tab_rows;
+    if (a.per_query) {   // the CMux tree's result, one sample per query
+        src = a.tab + (size_t)q * 2 * kN;
+        rows = 2;
+    } else {
+        int t = a.tab_index ? tgsw_sel(a.tab_index + q) : 0;
+        t = t < 0 ? 0 : t >= a.n_tab ? a.n_tab - 1 : t;   // clamped before any address is formed
+        src = a.tab + (size_t)t * a.tab_stride;
+    }
+    for (int j = tid; j < kN; j += kV4Threads) {
+        e_store(sh.E[0], j, rows == 2 ? (uint32_t)src[j] : 0u);
+        e_store(sh.E[1], j, (uint32_t)src[(rows - 1) * kN + j]);
+    }
+    __syncthreads();
+    for (int i = 0; i < a.d_h; ++i) {
+        const int idx = tgsw_sel(a.sel + (size_t)q * a.sel_stride + i);
+        if (idx < 0 || idx >= a.count) continue;
+        cmux_v4(sh, g, idx, k2N - (1 << (i + a.log_stride)), s, L);
+    }
+    for (int f = 0; f < a.n_out; ++f) {   // extraction at index f: a_j = E_a[(f - j) mod 2N], b = acc_b[f]
+        int32_t *uf = u_a + ((size_t)f * a.B + q) * kN;
+        for (int j = tid; j < kN; j += kV4Threads) uf[j] = (int32_t)sh.E[0][(f - j) & (k2N - 1)];
+    }
+    if (tid < a.n_out) u_b[(size_t)tid * a.B + q] = (int32_t)sh.E[1][tid];
+}
+
+// CMux batch: out[w] = d0[w] + C_{sel} (x) (d1[w] - d0[w]), the XP path of cmux_v4 on the difference.
+// Pair w belongs to query w / ppq.  n_poly > 0: the pair's operands are the polynomials 2 j, 2 j + 1
+// (j = w mod ppq) of the query's table, read in place; else d0 / d1 + w pair_stride (d0 null: the
+// plain external product).  Each workgroup reads its operands whole before it writes, so out may be
+// d0 or d1.  A selector outside [0, count) gives out = d0.
+__global__ __launch_bounds__(kV4Threads, 2) void k_tgsw_cmux_v4(V4Args g, TgswCmux a) {
+    __shared__ V4Shared sh;
+    const int tid = threadIdx.x;
+    const int s = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int L = tid & 63;
+    const int w = blockIdx.x;
+    const int q = w / a.ppq;
+    const int32_t *d0, *d1;
+    int rows = 2;
+    if (a.n_poly > 0) {
+        int t = a.tab_index ? tgsw_sel(a.tab_index + q) : 0;
+        t = t < 0 ? 0 : t >= a.n_tab ? a.n_tab - 1 : t;
+        rows = a.rows;
+        d0 = a.d0 + ((size_t)t * a.n_poly + 2 * (w - q * a.ppq)) * rows * kN;
+        d1 = d0 + (size_t)rows * kN;
+    } else {
+        d0 = a.d0 ? a.d0 + (size_t)w * a.pair_stride : nullptr;
+        d1 = a.d1 + (size_t)w * a.pair_stride;
+    }
+    const int idx = tgsw_sel(a.sel + (size_t)q * a.sel_stride);
+    const bool live = idx >= 0 && idx < a.count;
+    // word j of an operand, j < 2 kN; rows = 1: the mask is zero and the body is the one row
+    auto word = [&](const int32_t *d, int j) -> uint32_t {
+        if (!d || (rows == 1 && j < kN)) return 0u;
+        return (uint32_t)d[rows == 1 ? j - kN : j];
+    };
+    for (int j = tid; j < 2 * kN; j += kV4Threads)
+        e_store(sh.E[j >> kLogN], j & (kN - 1), word(d1, j) - word(d0, j));
+    __syncthreads();   // d1 is in the LDS: out may overwrite it
+    if (live) cmux_v4<true>(sh, g, idx, 0, s, L);
+    // d0 is read again word by word, each by the thread that then writes that word: out may be d0
+    int32_t *out = a.out + (size_t)w * 2 * kN;
+    for (int j = tid; j < 2 * kN; j += kV4Threads)
+        out[j] = (int32_t)(word(d0, j) + (live ? sh.E[j >> kLogN][j & (kN - 1)] : 0u));
+}
+
 unsigned brv10(unsigned x) {
     unsigned r = 0;
     for (int i = 0; i < kLogN; i++) { r = (r << 1) | (x & 1); x >>= 1; }
@@ -404,6 +491,39 @@ hipError_t launch_external_product_v4(const DeviceKey &key, int B, const int32_t
     if (!key.bk_v2) return hipErrorInvalidValue;
     trace_kernel("k_external_product_v4");
     hipLaunchKernelGGL(k_external_product_v4, dim3(B), dim3(kV4Threads), 0, s, v4_args(key), key_index, acc);
+    return hipGetLastError();
+}
+
+// the context's twiddles and CRT constants with an imported set in the key's place
+static bool tgsw_args(const DeviceKey &key, const uint32_t *set, int count, V4Args *g) {
+    if (!set || count <= 0 || !key.tw2 || !key.tw4) return false;
+    *g = v4_args(key);
+    g->bk = set;
+    return true;
+}
+
+hipError_t launch_tgsw_lookup_v4(const DeviceKey &key, const uint32_t *set, const TgswLookup &a, int32_t *u_a,
+                                 int32_t *u_b, hipStream_t s) {
+    if (a.B <= 0) return hipSuccess;
+    V4Args g;
+    if (!tgsw_args(key, set, a.count, &g) || !a.tab || !u_a || !u_b || (a.d_h > 0 && !a.sel) || a.d_h < 0 ||
+        a.log_stride < 0 || a.d_h + a.log_stride > kLogN || a.n_out < 1 || a.n_out > 16 ||
+        a.n_out > (1 << a.log_stride) || (!a.per_query && (a.n_tab < 1 || a.tab_rows < 1 || a.tab_rows > 2)))
+        return hipErrorInvalidValue;
+    trace_kernel("k_tgsw_lookup_v4");
+    hipLaunchKernelGGL(k_tgsw_lookup_v4, dim3(a.B), dim3(kV4Threads), 0, s, g, a, u_a, u_b);
+    return hipGetLastError();
+}
+
+hipError_t launch_tgsw_cmux_v4(const DeviceKey &key, const uint32_t *set, int pairs, const TgswCmux &a,
+                               hipStream_t s, const char *label) {
+    if (pairs <= 0) return hipSuccess;
+    V4Args g;
+    if (!tgsw_args(key, set, a.count, &g) || !a.sel || (!a.d1 && a.n_poly <= 0) || !a.out || a.ppq < 1 ||
+        (a.n_poly > 0 && (!a.d0 || a.n_tab < 1 || a.rows < 1 || a.rows > 2 || a.ppq * 2 != a.n_poly)))
+        return hipErrorInvalidValue;
+    trace_kernel(label ? label : "k_tgsw_cmux_v4");
+    hipLaunchKernelGGL(k_tgsw_cmux_v4, dim3(pairs), dim3(kV4Threads), 0, s, g, a);
     return hipGetLastError();
 }
 

@@ -71,5 +71,13 @@ hipError_t launch_bk_to_ntt(const int32_t *d_bk_coef, uint32_t *d_bk_ntt, const 
     return hipGetLastError();
 }
 
+// the same conversion over `count` caller-supplied TGSW samples (tgsw.cpp): the kernel indexes by
+// blockIdx only
+hipError_t launch_tgsw_to_ntt(const int32_t *d_coef, uint32_t *d_ntt, const NttTables *d_tab, int count,
+                              hipStream_t s) {
+    if (count <= 0 || count > (1 << 20)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bk_to_ntt, dim3(count * 2 * kKpl * 2), dim3(256), 0, s, d_coef, d_ntt, d_tab);
+    return hipGetLastError();
+}
 
 }  // namespace tfhe_amd

@@ -650,6 +650,27 @@ static int batch_dev(TfheAmdContext *c, void *stream, int slots, int B, int halv
     return TFHE_AMD_OK;
 }
 
+// the same frame for entry points that live outside this file (engine.h ContextFrame)
+int tfhe_amd_internal_frame(TfheAmdContext *c, void *stream, int u_slots, int (*fn)(const ContextFrame &, void *),
+                            void *arg) {
+    if (!c || !fn || u_slots < 0) return TFHE_AMD_E_ARG;
+    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    std::lock_guard<std::recursive_mutex> lk(c->mu);
+    DeviceScope dev_scope(c->device);
+    HIPCHK(dev_scope.rc);
+    TraceScope trace(c);
+    ContextFrame f{&c->key, c->device, s, nullptr, nullptr};
+    if (u_slots == 0) return fn(f, arg);
+    int rc = tfhe_amd_reserve(c, u_slots);
+    if (rc) return rc;
+    HIPCHK(c->fence.acquire(s));
+    f.u_a = c->u_a;
+    f.u_b = c->u_b;
+    rc = fn(f, arg);
+    HIPCHK(c->fence.done(s));
+    return rc;
+}
+
 extern "C" int tfhe_amd_gate_batch_dev(TfheAmdContext *c, int gate, int B, int32_t *res_a, int32_t *res_b,
                                        const int32_t *ca_a, const int32_t *ca_b, const int32_t *cb_a,
                                        const int32_t *cb_b, const int32_t *cc_a, const int32_t *cc_b,

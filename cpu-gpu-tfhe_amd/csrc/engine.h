@@ -176,6 +176,46 @@ hipError_t launch_blind_rotate_v4_debug(const DeviceKey &key, int B, int iters, 
 // tGswFFTExternMulToTLwe, exact (v4 arithmetic): acc [B][2][kN] <- BK_{key_index[b]} (x) acc
 hipError_t launch_external_product_v4(const DeviceKey &key, int B, const int32_t *key_index, int32_t *acc,
                                       hipStream_t s);
+// ---- leveled mode on caller-supplied TGSW samples (tgsw.cpp).  `set` is `count`
+// samples in the bk_v2 layout; twiddles and CRT constants are the key's (KS-only contexts have them).
+// Table lookup, one workgroup per query q < B: ACC = table t = tab_index[q] (null: 0; clamped into
+// [0, n_tab)) at tab + t tab_stride, tab_rows = 1 a plaintext polynomial (mask 0), 2 a TLWE sample
+// (a, b); per_query: ACC = the sample tab + q 2 kN instead (the CMux tree's result).  Then d_h CMux
+// steps with the selectors sel[q sel_stride + i] and rotations 2N - 2^(i + log_stride), and the
+// extraction of the coefficients f < n_out into u sample f B + q.
+struct TgswLookup {
+    int B = 0, count = 0;
+    const int32_t *sel = nullptr;
+    int sel_stride = 0, d_h = 0, log_stride = 0, n_out = 1;
+    const int32_t *tab = nullptr;
+    long tab_stride = 0;
+    int n_tab = 1, tab_rows = 1, per_query = 0;
+    const int32_t *tab_index = nullptr;
+};
+// CMux batch, one workgroup per pair w: out[w] = d0 + C_sel (x) (d1 - d0), out [pairs][2][kN];
+// the selector of pair w is sel[(w / ppq) sel_stride].  n_poly > 0 (the first tree level): d0 is the
+// table [n_tab][n_poly][rows][kN], pair w takes the polynomials 2 j, 2 j + 1 (j = w mod ppq, ppq =
+// n_poly / 2) of table tab_index[w / ppq]; n_poly = 0: operands at d0 / d1 + w pair_stride (d0 null:
+// the plain external product of d1).
+struct TgswCmux {
+    int count = 0;
+    const int32_t *sel = nullptr;
+    int sel_stride = 1, ppq = 1;
+    const int32_t *d0 = nullptr, *d1 = nullptr;
+    long pair_stride = 2 * kN;
+    int n_poly = 0, rows = 2, n_tab = 1;
+    const int32_t *tab_index = nullptr;
+    int32_t *out = nullptr;
+};
+hipError_t launch_tgsw_lookup_v4(const DeviceKey &key, const uint32_t *set, const TgswLookup &a, int32_t *u_a,
+                                 int32_t *u_b, hipStream_t s);
+// label: the name the launch trace gets (null: "k_tgsw_cmux_v4")
+hipError_t launch_tgsw_cmux_v4(const DeviceKey &key, const uint32_t *set, int pairs, const TgswCmux &a,
+                               hipStream_t s, const char *label = nullptr);
+// count-taking forms of launch_bk_to_ntt / launch_bk_v1_to_v2 (the same kernels over `count` samples)
+hipError_t launch_tgsw_to_ntt(const int32_t *d_coef, uint32_t *d_ntt, const NttTables *d_tab, int count,
+                              hipStream_t s);
+hipError_t launch_tgsw_v1_to_v2(const uint32_t *d_v1, uint32_t *d_v2, int count, hipStream_t s);
 // circuit level (v4 kernel): B instances x nrows rows, wires [W][B] ciphertexts, u slots r B + k
 hipError_t launch_blind_rotate_v4_rows(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
@@ -225,4 +265,20 @@ hipError_t launch_keyswitch(const DeviceKey &key, int B, const int32_t *u_a, con
                             const int32_t *u2_a, const int32_t *u2_b, int32_t add_b,
                             int32_t *res_a, int32_t *res_b, hipStream_t s);
 
+// What an entry point outside engine.cpp (tgsw.cpp) sees of a context while it holds it.
+struct ContextFrame {
+    const DeviceKey *key;
+    int device;
+    hipStream_t stream;       // the caller's stream, or the context's own
+    int32_t *u_a, *u_b;       // the extracted-sample scratch, at least u_slots samples (null if none asked)
+};
+
 }  // namespace tfhe_amd
+
+// Runs fn inside the frame every device entry point of engine.cpp sets up: context lock, its device
+// current, launch trace open; with u_slots > 0 also the scratch reserved for u_slots extracted
+// samples and fenced against its previous user on another stream (released after fn).  Returns
+// fn's TFHE_AMD_* code, or the frame's own failure.
+struct TfheAmdContext;
+int tfhe_amd_internal_frame(TfheAmdContext *c, void *stream, int u_slots,
+                            int (*fn)(const tfhe_amd::ContextFrame &, void *), void *arg);

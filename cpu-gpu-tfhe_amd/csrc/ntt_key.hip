@@ -71,4 +71,11 @@ hipError_t launch_bk_v1_to_v2(const uint32_t *d_v1, uint32_t *d_v2, hipStream_t 
     return hipGetLastError();
 }
 
+// the same repack over `count` caller-supplied TGSW samples (tgsw.cpp)
+hipError_t launch_tgsw_v1_to_v2(const uint32_t *d_v1, uint32_t *d_v2, int count, hipStream_t s) {
+    if (count <= 0 || count > (1 << 20)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bk_v1_to_v2, dim3(count * 2 * 8), dim3(256), 0, s, d_v1, d_v2);
+    return hipGetLastError();
+}
+
 }  // namespace tfhe_amd

@@ -469,17 +469,59 @@ static void create_ksk_nolock(LweKeySwitchKey *result, const int *in_key /*kN*/,
 // tLweSymEncryptZero (tlwe-functions.cu:26-38) with an EXACT b += key * a (the reference
 // uses its FFT multiply here, polynomials_arithmetic.h:112-114; key generation is
 // client side and off the hot path)
-static void tlwe_encrypt_zero_nolock(TLweSample *r, double alpha, const int *key /*kN binary*/) {
-    uint32_t *b = (uint32_t *)r->b->coefsT;
+// on the two polynomials themselves (a, b of kN words): the draws are b's kN Gaussians, then a's
+// kN uniform words, which key generation's order below depends on
+static void tlwe_zero_rows_nolock(uint32_t *a, uint32_t *b, double alpha, const int *key /*kN binary*/) {
     for (int j = 0; j < kN; ++j) b[j] = (uint32_t)gaussian32_nolock(0, alpha);
-    uint32_t *a = (uint32_t *)r->a[0].coefsT;
     for (int j = 0; j < kN; ++j) a[j] = (uint32_t)uniformTorus32_distrib(generator);   // torusPolynomialUniform
     for (int s = 0; s < kN; ++s) {
         if (!key[s]) continue;           // b += X^s * a (negacyclic)
         for (int i = 0; i < s; ++i) b[i] -= a[i - s + kN];
         for (int i = s; i < kN; ++i) b[i] += a[i - s];
     }
+}
+static void tlwe_encrypt_zero_nolock(TLweSample *r, double alpha, const int *key /*kN binary*/) {
+    tlwe_zero_rows_nolock((uint32_t *)r->a[0].coefsT, (uint32_t *)r->b->coefsT, alpha, key);
     r->current_variance = alpha * alpha;
+}
+
+// ---- client side of the leveled mode (include/tfhe_amd.h): TGSW encryptions of
+// bits and TLWE encryptions of polynomials under the keyset's TGSW key, in the layout of
+// tfhe_amd_export_bk's entries ([4 rows][2: a, b][kN] per sample).  What key generation does inline
+// for lwe_key->key[i] above: four zero rows at the key's alpha_min, then tGswAddMuIntH.
+EXPORT int tfhe_amd_tgsw_encrypt_bits(const TFheGateBootstrappingSecretKeySet *key, int n, const int32_t *bits,
+                                      int32_t *out) {
+    if (!key || !key->tgsw_key || n < 0 || !bits || !out) return TFHE_AMD_E_ARG;
+    for (int i = 0; i < n; ++i)
+        if (bits[i] != 0 && bits[i] != 1) return TFHE_AMD_E_ARG;
+    const TGswKey *gk = key->tgsw_key;
+    const double alpha = gk->tlwe_params->alpha_min;
+    const int *coefs = gk->tlwe_key.key[0].coefs;
+    std::lock_guard<std::mutex> lk(g_rng_mu);
+    for (int i = 0; i < n; ++i) {
+        uint32_t *g = (uint32_t *)out + (size_t)i * kKpl * 2 * kN;
+        for (int p = 0; p < kKpl; ++p) tlwe_zero_rows_nolock(g + (size_t)(p * 2) * kN, g + (size_t)(p * 2 + 1) * kN, alpha, coefs);
+        for (int bloc = 0; bloc <= kK; ++bloc)
+            for (int l = 0; l < kL; l++)
+                g[(size_t)((bloc * kL + l) * 2 + bloc) * kN] += (uint32_t)bits[i] * (uint32_t)gk->params->h[l];
+    }
+    return TFHE_AMD_OK;
+}
+
+// mu [n][kN] -> out [n][2: a, b][kN]: a zero row plus the message polynomial on b
+EXPORT int tfhe_amd_tlwe_encrypt_polys(const TFheGateBootstrappingSecretKeySet *key, int n, const int32_t *mu,
+                                       int32_t *out) {
+    if (!key || !key->tgsw_key || n < 0 || !mu || !out) return TFHE_AMD_E_ARG;
+    const TGswKey *gk = key->tgsw_key;
+    const double alpha = gk->tlwe_params->alpha_min;
+    const int *coefs = gk->tlwe_key.key[0].coefs;
+    std::lock_guard<std::mutex> lk(g_rng_mu);
+    for (int i = 0; i < n; ++i) {
+        uint32_t *r = (uint32_t *)out + (size_t)i * 2 * kN;
+        tlwe_zero_rows_nolock(r, r + kN, alpha, coefs);
+        for (int j = 0; j < kN; ++j) r[kN + j] += (uint32_t)mu[(size_t)i * kN + j];
+    }
+    return TFHE_AMD_OK;
 }
 
 EXPORT TFheGateBootstrappingSecretKeySet *

@@ -135,6 +135,19 @@ def _load():
     L.new_gate_bootstrapping_ciphertext_array.restype = _VP
     L.delete_gate_bootstrapping_ciphertext_array.argtypes = [ctypes.c_int, _VP]
     L.delete_gate_bootstrapping_cloud_keyset.argtypes = [_VP]
+    # leveled mode (tfhe_amd_tgsw_*)
+    L.tfhe_amd_tgsw_encrypt_bits.argtypes = [_VP, ctypes.c_int, _I32P, _I32P]
+    L.tfhe_amd_tlwe_encrypt_polys.argtypes = [_VP, ctypes.c_int, _I32P, _I32P]
+    L.tfhe_amd_tgsw_import.argtypes = [_VP, ctypes.c_int, _I32P, ctypes.POINTER(_VP)]
+    L.tfhe_amd_tgsw_count.argtypes = [_VP]
+    L.tfhe_amd_tgsw_destroy.argtypes = [_VP]
+    L.tfhe_amd_tgsw_cmux_dev.argtypes = [_VP, _VP, ctypes.c_int] + [_VP] * 4 + [_VP]
+    for f in ("tfhe_amd_tgsw_lookup_woks_dev", "tfhe_amd_tgsw_lookup_dev"):
+        getattr(L, f).argtypes = ([_VP, _VP, ctypes.c_int, ctypes.c_int, _VP] + [ctypes.c_int] * 3 + [_VP, _VP]
+                                  + [ctypes.c_int] * 2 + [_VP, _VP, _VP])
+    for f in ("tfhe_amd_tgsw_lookup_woks_host", "tfhe_amd_tgsw_lookup_host"):
+        getattr(L, f).argtypes = ([_VP, _VP, ctypes.c_int, ctypes.c_int, _I32P] + [ctypes.c_int] * 3 + [_I32P, _I32P]
+                                  + [ctypes.c_int] * 2 + [_I32P, _I32P])
     return L
 
 
@@ -462,6 +475,24 @@ class SecretKeyset:
         ph = (np.asarray(u_b).astype(np.int64) - u_a @ self.tlwe_key.astype(np.int64)) & 0xFFFFFFFF
         return ph.astype(np.uint32).view(np.int32)
 
+    # ---- client side of the leveled mode (tfhe_amd_tgsw_*; the library's generator, so
+    # tfhe_random_generator_setSeed / a fresh SecretKeyset(seed) makes them reproducible)
+    def tgsw_encrypt(self, bits):
+        """tfhe_amd_tgsw_encrypt_bits: TGSW encryptions of bits in {0, 1} -> [n][4][2][1024], the
+        layout of one entry of bk (Context.tgsw_import takes it)"""
+        bits = i32(np.asarray(bits).reshape(-1))
+        out = np.zeros((bits.shape[0], KPL, 2, N), np.int32)
+        _check(lib.tfhe_amd_tgsw_encrypt_bits(self.h, bits.shape[0], _p(bits), _p(out)), "tgsw_encrypt_bits")
+        return out
+
+    def tlwe_encrypt(self, polys):
+        """tfhe_amd_tlwe_encrypt_polys: TLWE encryptions of message polynomials [n][1024] (or one
+        [1024]) -> [n][2][1024] (a, then b)"""
+        mu = i32(polys).reshape(-1, N)
+        out = np.zeros((mu.shape[0], 2, N), np.int32)
+        _check(lib.tfhe_amd_tlwe_encrypt_polys(self.h, mu.shape[0], _p(mu), _p(out)), "tlwe_encrypt_polys")
+        return out
+
 
 class CloudKeyset:
     """new_tfheGateBootstrappingCloudKeySet_fromFile (tfhe_io.cu:1117): what cloud.cpp loads."""
@@ -494,6 +525,35 @@ class CloudKeyset:
 
 
 # --------------------------------------------------------------------- device context
+
+class TgswSet:
+    """TfheAmdTgsw: caller-supplied TGSW samples imported to a context's device
+    (Context.tgsw_import); close() frees them.  It does not depend on the context's lifetime."""
+
+    def __init__(self, h, device):
+        self.h, self.device = h, device
+
+    def __len__(self):
+        return int(lib.tfhe_amd_tgsw_count(self.h)) if self.h else 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.tfhe_amd_tgsw_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _log2(n_poly):
+    n_poly = int(n_poly)
+    if n_poly not in (1, 2, 4, 8, 16):
+        raise TfheAmdError(f"n_poly: need 1, 2, 4, 8 or 16, got {n_poly}")
+    return n_poly.bit_length() - 1
+
 
 class Context:
     """TfheAmdContext: key material of one cloud key on one GPU (tfhe_amd_context_create_raw)."""
@@ -742,6 +802,72 @@ class Context:
         _check(lib.tfhe_amd_full_add_batch_dev(self.h, B, _enc(enc_sum), _enc(enc_carry), a[0].data_ptr(),
                                                a[1].data_ptr(), b[0].data_ptr(), b[1].data_ptr(), cp[0], cp[1],
                                                res_a.data_ptr(), res_b.data_ptr(), stream), "full_add_batch_dev")
+
+    # ---- leveled mode (tfhe_amd_tgsw_*): CMux chains on caller-supplied TGSW samples
+    def tgsw_import(self, coef):
+        """tfhe_amd_tgsw_import: coef [n][4][2][1024] (SecretKeyset.tgsw_encrypt) -> TgswSet on
+        this context's device"""
+        coef = i32(coef)
+        if coef.ndim != 4 or coef.shape[1:] != (KPL, 2, N) or coef.shape[0] < 1:
+            raise TfheAmdError(f"coef: need int32 [n][4][2][1024], got {coef.shape}")
+        h = _VP()
+        _check(lib.tfhe_amd_tgsw_import(self.h, coef.shape[0], _p(coef), ctypes.byref(h)), "tgsw_import")
+        return TgswSet(h.value, self.device)
+
+    def tgsw_cmux_dev(self, tset, sel, d1, d0, out, stream=None):
+        """tfhe_amd_tgsw_cmux_dev on torch tensors: out[w] = d0[w] + C_sel[w] (x) (d1[w] - d0[w]);
+        d0 = None: the external product; out may be d0 or d1"""
+        B = sel.shape[0]
+        named = [("sel", sel, (B,)), ("d1", d1, (B, 2, N)), ("out", out, (B, 2, N))]
+        if d0 is not None:
+            named.append(("d0", d0, (B, 2, N)))
+        for name, t, shape in named:
+            self._dev_check(t, shape, name)
+        _check(lib.tfhe_amd_tgsw_cmux_dev(self.h, tset.h, B, sel.data_ptr(), d1.data_ptr(),
+                                          None if d0 is None else d0.data_ptr(), out.data_ptr(), stream),
+               "tgsw_cmux_dev")
+
+    def tgsw_lookup_host(self, tset, sel, tab, tab_index=None, log_stride=0, n_out=1, woks=False):
+        """tfhe_amd_tgsw_lookup[_woks]_host: sel [B][d] selector indices (bit 0 first), tab
+        [n_tab][n_poly][tab_rows][1024] -> (r_a [n_out][B][500], r_b [n_out][B]), or with woks the
+        extracted samples (u_a [n_out][B][1024], u_b [n_out][B])"""
+        sel = i32(sel); tab = i32(tab)
+        if sel.ndim != 2 or tab.ndim != 4 or tab.shape[3] != N:
+            raise TfheAmdError(f"need sel [B][d] and tab [n_tab][n_poly][tab_rows][1024], got {sel.shape}, {tab.shape}")
+        B, d = sel.shape
+        n_tab, n_poly, rows, _ = tab.shape
+        _log2(n_poly)
+        idx = None if tab_index is None else i32(tab_index)
+        if idx is not None and idx.shape != (B,):
+            raise TfheAmdError(f"tab_index: need one table index per query ({B}), got {idx.shape}")
+        n_out = int(n_out)
+        r_a = np.zeros((max(n_out, 1), B, N if woks else n_lwe), np.int32)
+        r_b = np.zeros((max(n_out, 1), B), np.int32)
+        name = "tgsw_lookup" + ("_woks" if woks else "") + "_host"
+        _check(getattr(lib, "tfhe_amd_" + name)(self.h, tset.h, B, d, _p(sel), n_tab, n_poly, rows, _p(tab), _p(idx),
+                                                int(log_stride), n_out, _p(r_a), _p(r_b)), name)
+        return r_a, r_b
+
+    def tgsw_lookup_dev(self, tset, sel, tab, out_a, out_b, tab_index=None, log_stride=0, n_out=1, woks=False,
+                        stream=None):
+        """tfhe_amd_tgsw_lookup[_woks]_dev on torch tensors (shapes as tgsw_lookup_host); asynchronous"""
+        if sel is None or sel.dim() != 2 or tab is None or tab.dim() != 4:
+            raise TfheAmdError("need GPU tensors sel [B][d] and tab [n_tab][n_poly][tab_rows][1024]")
+        B, d = sel.shape
+        n_tab, n_poly, rows, _ = tab.shape
+        _log2(n_poly)
+        n_out = int(n_out)
+        named = [("sel", sel, (B, d)), ("tab", tab, (n_tab, n_poly, rows, N)),
+                 ("out_a", out_a, (max(n_out, 1), B, N if woks else n_lwe)), ("out_b", out_b, (max(n_out, 1), B))]
+        if tab_index is not None:
+            named.append(("tab_index", tab_index, (B,)))
+        for name, t, shape in named:
+            self._dev_check(t, shape, name)
+        name = "tgsw_lookup" + ("_woks" if woks else "") + "_dev"
+        _check(getattr(lib, "tfhe_amd_" + name)(self.h, tset.h, B, d, sel.data_ptr(), n_tab, n_poly, rows,
+                                                tab.data_ptr(), None if tab_index is None else tab_index.data_ptr(),
+                                                int(log_stride), n_out, out_a.data_ptr(), out_b.data_ptr(), stream),
+               name)
 
     def blind_rotate_dev(self, acc, bara, iters, stream=None):
         B = acc.shape[0]

@@ -279,6 +279,94 @@ int tfhe_amd_blind_rotate_dev(TfheAmdContext *ctx, int B, int iters, int32_t *ac
 int tfhe_amd_external_product_dev(TfheAmdContext *ctx, int B, const int32_t *key_index, int32_t *acc,
                                   void *stream);
 
+/* ---- Leveled mode: CMux chains on caller-supplied TGSW ciphertexts.
+ * Every bootstrap costs 500 CMux steps on the 500 TGSW samples of the bootstrapping key.  When the
+ * CLIENT supplies the address bits of a table lookup as TGSW ciphertexts, a lookup in a table of
+ * 2^d entries is d CMux steps: with the table in a polynomial, step i multiplies the accumulator by
+ * X^{-2^i} when bit i is 1, and sample extraction reads the entry at coefficient 0.  The output
+ * carries about the noise of a gate's output before its key switch; after the key switch it is an
+ * ordinary n = 500 sample that every gate, LUT row and full_add cell can read.
+ * LIMIT: the address bits must arrive as TGSW ciphertexts from the client.  A computed LWE bit
+ * cannot be turned into one (that is circuit bootstrapping, which this library does not have), so
+ * this serves the input layer of a computation: S-boxes, ROMs, private reads on client indices.
+ *
+ * Client side (host only, no GPU; both draw from the library's generator, so
+ * tfhe_random_generator_setSeed makes them reproducible):
+ * tfhe_amd_tgsw_encrypt_bits: n TGSW encryptions of bits[i] in {0, 1} under the keyset's TGSW key
+ *   at its alpha_min, exactly as key generation encrypts the LWE key bits; out is
+ *   int32 [n][4][2][1024], the layout of one entry of tfhe_amd_export_bk (row, then a / b).
+ * tfhe_amd_tlwe_encrypt_polys: n TLWE encryptions of the message polynomials mu [n][1024] under
+ *   the same key and noise, out [n][2][1024] (a, then b): encrypted tables.
+ * TFHE_AMD_E_ARG for a null pointer, n < 0 or a bit outside {0, 1} (nothing is drawn then). */
+int tfhe_amd_tgsw_encrypt_bits(const TFheGateBootstrappingSecretKeySet *key, int n, const int32_t *bits,
+                               int32_t *out);
+int tfhe_amd_tlwe_encrypt_polys(const TFheGateBootstrappingSecretKeySet *key, int n, const int32_t *mu,
+                                int32_t *out);
+
+/* An imported set: n coefficient-domain TGSW samples (host, [n][4][2][1024]) uploaded to the
+ * context's device and converted there into the exact kernels' layout (two 27-bit primes, 64 KB per
+ * sample).  Synchronous.  The set lives on that device and does not depend on the context's
+ * lifetime; it may be used with any context on the same device (also a key-switch-only one for the
+ * woks forms), and a call that pairs it with a context on another device returns TFHE_AMD_E_ARG.
+ * Destroy waits for the device.  count: the number of samples, or TFHE_AMD_E_ARG for NULL. */
+typedef struct TfheAmdTgsw TfheAmdTgsw;
+int tfhe_amd_tgsw_import(TfheAmdContext *ctx, int n, const int32_t *coef_host, TfheAmdTgsw **out);
+int tfhe_amd_tgsw_count(const TfheAmdTgsw *set);
+int tfhe_amd_tgsw_destroy(TfheAmdTgsw *set);
+
+/* B CMux gates on TLWE samples [B][2][1024] (a, then b; device arrays, asynchronous):
+ * out[w] = d0[w] + C (x) (d1[w] - d0[w]) with C sample sel[w] of the set, i.e. d1 where C encrypts
+ * 1 and d0 where it encrypts 0, exact arithmetic.  d0 = NULL: the plain external product
+ * C (x) d1[w].  out may be d0 or d1 (the same array; other overlaps are not supported).  sel is a
+ * device array: an index outside [0, count) gives out[w] = d0[w] (zero for d0 = NULL), checked on
+ * the device before any address is formed. */
+int tfhe_amd_tgsw_cmux_dev(TfheAmdContext *ctx, TfheAmdTgsw *set, int B, const int32_t *sel,
+                           const int32_t *d1, const int32_t *d0, int32_t *out, void *stream);
+
+/* B table lookups.  Query q reads table t = tab_index[q] (NULL: table 0) at the d-bit address
+ * addr = sum_i bit_i 2^i whose bit i is encrypted by sample sel[q * d + i] of the set (bit 0
+ * first; queries may share samples).
+ *   tab: int32 [n_tab][n_poly][tab_rows][1024].  tab_rows = 1: plaintext polynomials of Torus32
+ *     entries (the trivial sample (0, tab)); tab_rows = 2: TLWE samples (a, then b) from
+ *     tfhe_amd_tlwe_encrypt_polys.
+ *   Horizontal packing: a polynomial holds 2^d_h entries of 2^log_stride words each, entry e at
+ *     the coefficients e << log_stride ..., and output f < n_out encrypts
+ *     tab[t][(addr_h << log_stride) + f].  d_h + log_stride <= 10, 1 <= n_out <= min(16, 2^log_stride).
+ *   Vertical packing: n_poly in {1, 2, 4, 8, 16} polynomials per table and d = d_h + log2(n_poly);
+ *     the address bits d_h .. d - 1 pick the polynomial through a CMux tree (bit d_h pairs the
+ *     polynomials 2 j, 2 j + 1), one k_tgsw_cmux_v4 launch per level, then the rotation kernel runs
+ *     on the tree's result.  The tree's scratch belongs to the set and grows on demand.
+ * Outputs are function-major like tfhe_amd_bootstrap_lut_many_*: the woks forms return the
+ * extracted samples u_a [n_out][B][1024], u_b [n_out][B] under the extracted TLWE key; the other
+ * forms run ONE key switch over the n_out B samples and return res_a [n_out][B][500],
+ * res_b [n_out][B].  The _dev forms take device arrays and are asynchronous on `stream`; a
+ * selector index outside [0, count) skips its CMux step and a tab_index entry is clamped into
+ * [0, n_tab), both on the device before any address is formed.  The _host forms take host arrays,
+ * stage through temporary device buffers, are synchronous and return TFHE_AMD_E_ARG for any
+ * selector index outside [0, count) or tab_index entry outside [0, n_tab).  TFHE_AMD_E_ARG also
+ * for a shape outside the limits above, a null array, and a context without key-switching key in
+ * the key-switched forms.
+ * There is no fp64 form of these kernels: tfhe_amd_select_kernel and the exactness guard do not
+ * apply, the arithmetic is always the exact two-prime NTT.  tfhe_amd_last_kernels reports, in
+ * launch order, "k_tgsw_cmux_v4(tree-level-0)", ... once per tree level, "k_tgsw_lookup_v4" and the
+ * key switch's own name; tfhe_amd_tgsw_cmux_dev reports "k_tgsw_cmux_v4". */
+int tfhe_amd_tgsw_lookup_woks_dev(TfheAmdContext *ctx, TfheAmdTgsw *set, int B, int d, const int32_t *sel,
+                                  int n_tab, int n_poly, int tab_rows, const int32_t *tab,
+                                  const int32_t *tab_index, int log_stride, int n_out,
+                                  int32_t *u_a, int32_t *u_b, void *stream);
+int tfhe_amd_tgsw_lookup_dev(TfheAmdContext *ctx, TfheAmdTgsw *set, int B, int d, const int32_t *sel,
+                             int n_tab, int n_poly, int tab_rows, const int32_t *tab,
+                             const int32_t *tab_index, int log_stride, int n_out,
+                             int32_t *res_a, int32_t *res_b, void *stream);
+int tfhe_amd_tgsw_lookup_woks_host(TfheAmdContext *ctx, TfheAmdTgsw *set, int B, int d, const int32_t *sel,
+                                   int n_tab, int n_poly, int tab_rows, const int32_t *tab,
+                                   const int32_t *tab_index, int log_stride, int n_out,
+                                   int32_t *u_a, int32_t *u_b);
+int tfhe_amd_tgsw_lookup_host(TfheAmdContext *ctx, TfheAmdTgsw *set, int B, int d, const int32_t *sel,
+                              int n_tab, int n_poly, int tab_rows, const int32_t *tab,
+                              const int32_t *tab_index, int log_stride, int n_out,
+                              int32_t *res_a, int32_t *res_b);
+
 /* Timing of the engine's own kernels (HIP events on the stream they run on):
  * enable=1 starts accumulating; read returns the summed ms and launch counts of the
  * blind-rotation kernel and the key-switch kernel since enabling. */
