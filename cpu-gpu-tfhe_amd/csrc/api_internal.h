@@ -56,9 +56,10 @@ int tfhe_amd_internal_tier1_batch(const TFheGateBootstrappingCloudKeySet *bk, in
 // Tier-1 queue merges two batches while together they hold at most one ciphertext per CU
 int tfhe_amd_internal_device_cus(int device);
 // the extracted samples of a context's last gate batch (<= one round), halves x B rows of 1024
+// (host_batch.cpp)
 int tfhe_amd_internal_last_extracted(TfheAmdContext *c, int B, int halves, int32_t *u_a);
-// device copy of host bytes on a context's GPU / its release; device-side current_variance of the
-// context's last gate batch (engine.cpp)
+// device copy of host bytes on a context's GPU / its release (engine.cpp); device-side
+// current_variance of the context's last gate batch (host_batch.cpp)
 int tfhe_amd_internal_upload(TfheAmdContext *c, const void *host, size_t bytes, void **dev);
 void tfhe_amd_internal_free(int device, void *dev);
 int tfhe_amd_internal_ks_variance(TfheAmdContext *c, int B, int halves, const double *d_var, double *out);

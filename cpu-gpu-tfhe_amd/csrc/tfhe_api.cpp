@@ -40,7 +40,7 @@ using namespace tfhe_amd;
 using namespace tfhe_amd::api;
 
 TfheAmdContext *tfhe_amd_context_lane(TfheAmdContext *primary);   // engine.cpp
-int tfhe_amd_internal_unsliced_max();                                 // engine.cpp
+int tfhe_amd_internal_unsliced_max();                                 // host_batch.cpp
 
 // ------------------------------------------------------------------ numerics
 // numeric-functions.cu:11-77

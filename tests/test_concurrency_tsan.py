@@ -14,7 +14,8 @@ that come and go.  Every result is compared word for word (current_variance bit 
 the same work done sequentially, and DeviceScope's save / restore logic is unit-tested with the
 stub's per-thread current device.  Pass = exit 0 and no ThreadSanitizer report.
 
-Round 5: csrc/engine.cpp itself is built the same way (tests/tsan/_bin/tsan_engine:
+Round 5: csrc/engine.cpp and csrc/host_batch.cpp (the host-pointer paths)
+themselves are built the same way (tests/tsan/_bin/tsan_engine:
 the whole host library + CPU stand-in kernels, tests/tsan/stub_kernels.cpp) against a stub HIP
 runtime whose streams are asynchronous worker threads, so a host read that is not ordered after
 the stream work producing it is a race TSan sees.  tsan_engine_driver.cpp hammers the host copy
@@ -72,21 +73,22 @@ def test_engine_host_side_is_tsan_clean():
     assert "WARNING: ThreadSanitizer" not in out, out[-6000:]
     assert r.returncode == 0, out[-4000:]
     assert "tsan_engine_driver: ok" in r.stdout
-    for phase in ("sequential: 10 workloads", "engine host paths: 8 threads", "all equal", "pinned registry:"):
+    for phase in ("sequential: 12 workloads", "engine host paths: 8 threads", "all equal", "pinned registry:"):
         assert phase in r.stdout, r.stdout
 
 
 @pytest.mark.skipif(not _tsan_available(), reason="needs g++ and make")
 def test_engine_tsan_harness_catches_a_missing_synchronization():
-    """Mutation check: without the pinned host path's hipStreamSynchronize the host reads results the
-    (asynchronous) stub stream is still writing — the harness must report it."""
-    src = open(os.path.join(HERE, "..", "cpu-gpu-tfhe_amd", "csrc", "engine.cpp")).read()
-    cut = "    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);\n    tr.lap(tr.wait);\n"
+    """Mutation check: without the pinned host path's final wait for its streams (drain: the copy
+    stream, then hipStreamSynchronize(c->stream)) the host reads results the (asynchronous) stub
+    stream is still writing — the harness must report it."""
+    src = open(os.path.join(HERE, "..", "cpu-gpu-tfhe_amd", "csrc", "host_batch.cpp")).read()
+    cut = "    const hipError_t w = drain(c);\n    tr.lap(tr.wait);\n"
     assert src.count(cut) == 1, "the pinned path's final synchronization moved: update the mutation"
     os.makedirs(os.path.join(TSAN, "_bin"), exist_ok=True)
-    mut = "// engine.cpp with the pinned path's final stream synchronization removed (mutation check)\n" + \
-        src.replace(cut, "    tr.lap(tr.wait);\n")
-    path = os.path.join(TSAN, "_bin", "engine_mut.cpp")
+    mut = "// host_batch.cpp with the pinned path's final stream synchronization removed (mutation check)\n" + \
+        src.replace(cut, "    const hipError_t w = hipSuccess;\n    tr.lap(tr.wait);\n")
+    path = os.path.join(TSAN, "_bin", "host_batch_mut.cpp")
     if not os.path.exists(path) or open(path).read() != mut:
         open(path, "w").write(mut)
     subprocess.run(["make", "-s", "-j4", "-C", TSAN, "_bin/tsan_engine_mut"], check=True, timeout=600)

@@ -282,6 +282,61 @@ def test_boots_batch_lwesample_arrays(keyset, ctx, rng):
 
 
 @pytest.mark.gpu
+def test_boots_batch_three_slices(keyset, ctx, rng):
+    """tfhe_amd_boots_batch NAND at B = 2 049: slices of 1 024 / 1 024 / 1, the smallest record batch of
+    three slices, i.e. the first at which the slice pipeline records ev_out[s & 1] a second time (slice
+    2 reuses slice 0's event).  Every Torus32 word equals the array host path's (ctx.gate_host) on the
+    same inputs, current_variance on both sides of each slice seam is bit for bit the single
+    bootsNAND's, and one more call in place (result = the first input array) gives the same."""
+    import ctypes
+    import numpy as np
+    import tfhe_amd as T
+
+    class LweSample(ctypes.Structure):
+        _fields_ = [("a", ctypes.POINTER(ctypes.c_int32)), ("b", ctypes.c_int32), ("current_variance", ctypes.c_double)]
+    P = ctypes.c_void_p
+    lib = T.lib
+    lib.tfhe_amd_boots_batch.argtypes = [ctypes.c_int, P, P, P, P, ctypes.c_int, P]
+    lib.bootsNAND.argtypes = [P, P, P, P]
+    lib.new_gate_bootstrapping_ciphertext_array.restype = P
+    cloud = keyset.cloud
+    B = 2049
+    host = [keyset.encrypt(rng.integers(0, 2, B), rng) for _ in range(2)]
+    arrs = []
+    for _ in range(3):
+        p = lib.new_gate_bootstrapping_ciphertext_array(B, P(keyset.params))
+        arrs.append((p, (LweSample * B).from_address(p)))
+    for (p, s), (a, b) in zip(arrs[:2], host):
+        for k in range(B):
+            ctypes.memmove(s[k].a, a[k].ctypes.data, 4 * 500)
+            s[k].b = int(b[k])
+
+    def words(s):
+        return (np.array([np.ctypeslib.as_array(s[k].a, (500,)) for k in range(B)]),
+                np.array([s[k].b for k in range(B)], dtype=np.int32))
+
+    res_p, res = arrs[2]
+    assert lib.tfhe_amd_boots_batch(T.GATES["NAND"], P(res_p), P(arrs[0][0]), P(arrs[1][0]), None, B, P(cloud)) == 0
+    want = ctx.gate_host("NAND", *[v for hb in host for v in hb])
+    got = words(res)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+    one_p = lib.new_gate_bootstrapping_ciphertext_array(1, P(keyset.params))
+    one = (LweSample * 1).from_address(one_p)
+    for k in (0, 1023, 1024, 2047, 2048):
+        lib.bootsNAND(P(one_p), P(ctypes.addressof(arrs[0][1][k])), P(ctypes.addressof(arrs[1][1][k])), P(cloud))
+        assert one[0].current_variance == res[k].current_variance > 0, k
+    # in place: each slice's results land in the rows its inputs were gathered from
+    assert lib.tfhe_amd_boots_batch(T.GATES["NAND"], P(arrs[0][0]), P(arrs[0][0]), P(arrs[1][0]), None, B,
+                                    P(cloud)) == 0
+    got = words(arrs[0][1])
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), "in place"
+    assert all(arrs[0][1][k].current_variance == res[k].current_variance for k in range(B))
+    for p, _ in arrs:
+        lib.delete_gate_bootstrapping_ciphertext_array(B, P(p))
+    lib.delete_gate_bootstrapping_ciphertext_array(1, P(one_p))
+
+
+@pytest.mark.gpu
 def test_tier1_raw_bootstrap_exports(keyset, okey, rng):
     """The raw Tier-1 exports Cipher.cpp calls directly (addBitsRaw / bootsANDXOR, Cipher.cpp:647-766;
     SURVEY.md §8(b)): tfhe_bootstrap_woKS_FFT (dimension-1 024 output), tfhe_bootstrap_FFT and

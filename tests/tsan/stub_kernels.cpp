@@ -1,6 +1,6 @@
-// Test-only CPU stand-ins for the HIP kernels' launchers (csrc/*.hip), so that csrc/engine.cpp itself
-// — the host copy pool, the pinned registry, the sliced / record / pinned host paths, the context
-// lock, replicas — builds against the stub HIP runtime (stub/hip/hip_runtime.h) and runs under
+// Test-only CPU stand-ins for the HIP kernels' launchers (csrc/*.hip), so that csrc/engine.cpp (the
+// context lock, replicas) and csrc/host_batch.cpp (the host copy pool, the pinned registry, the
+// sliced / record / pinned host paths) themselves build against the stub HIP runtime (stub/hip/hip_runtime.h) and runs under
 // ThreadSanitizer (tests/tsan/tsan_engine_driver.cpp, tests/test_concurrency_tsan.py).  Each
 // launcher enqueues its work on the stream it is given, like a kernel launch: it runs later on that
 // stream's worker thread, so the engine's stream / event ordering is what makes its results visible

@@ -1,7 +1,7 @@
 // ThreadSanitizer driver for the device engine's host side (VERDICT r4 item 4;
-// tests/test_concurrency_tsan.py): csrc/engine.cpp itself — its host copy pool (HostCopyPool,
-// shared by every context), the pinned-buffer registry, the staged / sliced / record / pinned host
-// paths, the context lock, key replicas — built unchanged with -fsanitize=thread against the
+// tests/test_concurrency_tsan.py): csrc/engine.cpp and csrc/host_batch.cpp themselves — the host
+// copy pool (HostCopyPool, shared by every context), the pinned-buffer registry, the staged / sliced
+// / record / pinned host paths, the context lock, key replicas — built unchanged with -fsanitize=thread against the
 // asynchronous stub HIP runtime (stub/hip/hip_runtime.h: streams are worker threads) and CPU
 // stand-in kernels (stub_kernels.cpp), together with the rest of the host library.
 //
@@ -11,7 +11,8 @@
 //      the others run): staged (one round, two halves through the copy pool), sliced (1 100 and a
 //      2 100-gate MUX: slices of 1 024 pipelined over the copy stream), caller-owned pinned arrays,
 //      and record batches (LweSample-like rows: gather into pinned staging, scatter back,
-//      current_variance on the device) — several threads on ONE context at once;
+//      current_variance on the device) — the pinned and the record form also at 2 100 gates, three
+//      slices, where ev_out[s & 1] is used a second time — several threads on ONE context at once;
 //   2. the pinned registry under churn: host_alloc / host_free from some threads while others
 //      query is_pinned and run pinned batches.
 // Exit 0 = all equal; ThreadSanitizer itself exits 66 on any report.
@@ -163,7 +164,8 @@ int main(int argc, char **argv) {
                              {TFHE_GATE_XOR, 1100, STAGED},  {TFHE_GATE_MUX, 2100, STAGED},
                              {TFHE_GATE_NAND, 64, PINNED},   {TFHE_GATE_OR, 700, PINNED},
                              {TFHE_GATE_MUX, 1100, PINNED},  {TFHE_GATE_NOR, 96, RECORDS},
-                             {TFHE_GATE_XNOR, 1100, RECORDS}, {TFHE_GATE_MUX, 600, RECORDS}};
+                             {TFHE_GATE_XNOR, 1100, RECORDS}, {TFHE_GATE_MUX, 600, RECORDS},
+                             {TFHE_GATE_MUX, 2100, RECORDS}, {TFHE_GATE_NAND, 2100, PINNED}};
     std::vector<Work> works;
     for (size_t i = 0; i < sizeof shapes / sizeof shapes[0]; ++i) {
         Work w;
