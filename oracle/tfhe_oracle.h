@@ -13,9 +13,12 @@
  *     oracle/_ref/libtfheref.so) through committed fixtures in tests/golden/;
  *   - LWE-level ops (lweNoiselessTrivial/AddTo/SubTo/AddMulTo, lwe-functions.cu) are
  *     pinned the same way;
- *   - the remaining steps (rotation, gadget decomposition, extraction, key switch) are
- *     restatements cited line by line and checked by decryption truth tables; there is
- *     no reference golden vector for them ("parity partial").
+ *   - rotation, gadget decomposition, extraction, key switch, external product, CMux, blind
+ *     rotation, the woKS and the full bootstrap and NAND / XOR / MUX are pinned to the
+ *     reference's own functions, cut out by name (oracle/extract_ref.py) and compiled
+ *     unmodified, through tests/golden/ref_hotpath_vectors.npz (tests/test_ref_hotpath.py);
+ *   - not pinned: the spqlios FFT product and its conversion to Torus32.  The reference's
+ *     functions above were linked with its exact Karatsuba product in the FFT product's place.
  *
  * Layouts (canonical coefficient domain, int32 little endian):
  *   BK  : int32 [n=500][kpl=4][k+1=2][N=1024]   (TGswSample.all_sample[p].a[c].coefsT)

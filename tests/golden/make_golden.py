@@ -1,15 +1,26 @@
-"""Generate the golden fixtures in tests/golden/ from the reference's OWN compiled leaf
-sources (oracle/_ref/libtfheref.so, built by oracle/build_ref.sh from
-/root/reference/gpuParallel/{numeric-functions,multiplication,lwe-functions,...,tgsw,tlwe,
-lwekeyswitch}.cu).
+"""Generate the golden fixtures in tests/golden/ from the reference's OWN compiled code
+(oracle/_ref/libtfheref.so, built by oracle/build_ref.sh from the reference's gpuParallel/: its
+leaf sources whole, and its hot-path functions cut out by name by oracle/extract_ref.py).
 
-Run in the build container (the reference is not on the GPU box):
-    oracle/build_ref.sh && python tests/golden/make_golden.py
-Writes tests/golden/ref_leaf_vectors.npz (data only: inputs + reference outputs).
+Run where the reference is present (it is not on a GPU machine), after the project's build:
+    oracle/build_ref.sh && python tests/golden/make_golden.py [leaf | hotpath]
+leaf     writes ref_leaf_vectors.npz and abi_layout.json: exact products, modSwitch, the RNG, the
+         LWE linear ops, the gadget constants, the key-switching key's index map, struct layouts;
+hotpath  writes ref_hotpath_vectors.npz (about two minutes): both rotations, the decomposition
+         (scalar and AVX2 builds asserted equal), sample extraction, the key switch, the external
+         product, CMux chains, tfhe_blindRotateAndExtract with constant and table test vectors,
+         the woKS and the full bootstrap, and NAND / XOR / MUX gates, all under the product's
+         seeded keyset (seed 314, 1592, 657), whose bk / ksk are recorded by their sha256.  Written
+         with fixed zip timestamps: the same inputs give the same bytes.
+Both files hold data only: inputs and the reference's outputs (tests/ref_fixture.py has the layout).
 """
 import ctypes
+import io
 import math
 import os
+import sys
+import zipfile
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -138,5 +149,174 @@ def main():
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def save_npz(path, arrays):
+    """np.savez_compressed with fixed member timestamps (numpy stamps the current time)"""
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name, a in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(a), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue())
+
+
+def hotpath():
+    for d in (os.path.join(REPO, "tests"), os.path.join(REPO, "cpu-gpu-tfhe_amd")):
+        if d not in sys.path:
+            sys.path.insert(0, d)
+    import ref_fixture as RF
+    import tfhe_amd as T
+
+    n, OFF = RF.n_lwe, RF.OFFSET
+    rng = np.random.default_rng(20240607)
+    pool = ThreadPoolExecutor(min(16, os.cpu_count() or 4))   # ctypes releases the GIL
+
+    def words(*shape):
+        return rng.integers(-2**31, 2**31, shape, dtype=np.int64).astype(np.int32)
+
+    K = T.SecretKeyset()          # seed (314, 1592, 657)
+    R = RF.Ref(K.bk, K.ksk)
+    out = {"key_bk_sha": np.array(RF.sha(K.bk)), "key_ksk_sha": np.array(RF.sha(K.ksk))}
+
+    # (1) rotations by X^a and X^a - 1, a in [0, 2N): the edges in full, random values hashed
+    a_rot = np.array([0, 1, N - 1, N, N + 1, 2 * N - 1, 3, 1500] + list(rng.integers(2, 2 * N - 1, 6)), np.int32)
+    x = words(N)
+    out["rot_in"], out["rot_a"] = x, a_rot
+    RF.pack(out, "rot_xai", [R.mul_by_xai(a, x) for a in a_rot], 8)
+    RF.pack(out, "rot_xai_m1", [R.mul_by_xai(a, x, minus_one=True) for a in a_rot], 8)
+
+    # (2) decomposition: case 0 opens with the edge words, then random words
+    edges = [0, 1, -1, -2**31, 2**31 - 1, -OFF, -OFF - 1, -OFF + 1]
+    for unit, ks in ((1 << 12, (0, 1, 2, 511, 512, 1023, 1024, 1 << 19, (1 << 20) - 1)),
+                     (1 << 22, (0, 1, 2, 511, 512, 513, 1022, 1023))):
+        edges += [k * unit - OFF + d for k in ks for d in (-1, 0, 1)]
+    dec_in = words(4, N)
+    dec_in[0, :len(edges)] = RF.i32(edges)
+    out["dec_n_edges"] = np.array(len(edges), np.int32)
+    avx2 = ctypes.CDLL(RF.REF_AVX2_SO)
+    dec = [R.decompose(v) for v in dec_in]
+    for v, d in zip(dec_in, dec):
+        assert np.array_equal(RF.decompose(avx2, v), d), "scalar and AVX2 decompositions differ"
+    out["dec_in"] = dec_in
+    RF.pack(out, "dec_out", dec, 4)
+
+    # (3) sample extraction at an index
+    acc = words(2, N)
+    idx = np.array([0, 1, 15, N - 1], np.int32)
+    ext = [R.extract(acc, f) for f in idx]
+    out["ext_acc"], out["ext_index"] = acc, idx
+    RF.pack(out, "ext_out_a", [e[0] for e in ext], 4)
+    out["ext_out_b"] = RF.i32([e[1] for e in ext])
+
+    # (4) key switch: random samples, an all-zero mask (every digit 0: only the rounding offset
+    # acts), a mask whose digits are all 3 (aibar = a + 2^15 in [0xFFFF8000, 2^32))
+    u_a = words(6, N)
+    u_b = words(6)
+    u_a[4] = 0
+    u_a[5] = RF.i32(0xFFFF0000 + rng.integers(0, 1 << 15, N))
+    ks = list(pool.map(lambda c: R.keyswitch(u_a[c], u_b[c]), range(6)))
+    out["ks_u_a"], out["ks_u_b"] = u_a, u_b
+    RF.pack(out, "ks_out_a", [k[0] for k in ks], 6)
+    out["ks_out_b"] = RF.i32([k[1] for k in ks])
+
+    # (5a) external product on key rows: random accumulators, and accumulators whose digits all
+    # saturate (x + offset in [0, 2^12): both digits -512; in [2^32 - 2^12, 2^32): both 511)
+    xp_acc = words(4, 2, N)
+    xp_acc[2] = RF.i32(-OFF + rng.integers(0, 1 << 12, (2, N)))
+    xp_acc[3] = RF.i32(-OFF - (1 << 12) + rng.integers(0, 1 << 12, (2, N)))
+    xp_row = np.array([0, 7, 3, 5], np.int32)
+    out["xp_acc"], out["xp_row"] = xp_acc, xp_row
+    RF.pack(out, "xp_out", list(pool.map(lambda c: R.external_product(xp_acc[c], xp_row[c]), range(4))), 4)
+
+    # (5b) CMux chains over key rows 0 .. 7 in order (tfhe_blindRotate, n = 8): rotation edges and
+    # a skipped step, a run of skipped steps, random ones, and an accumulator whose first step
+    # (a = N: (X^N - 1) acc = -2 acc) decomposes to digits -512 (mask) and 511 (body)
+    cm_acc = words(8, 2, N)
+    cm_bara = rng.integers(1, 2 * N, (8, 8)).astype(np.int32)
+    cm_bara[0] = [0, 1, N - 1, N, N + 1, 2 * N - 1, 5, 0]
+    cm_bara[1, :4] = 0
+    cm_bara[4, 0] = N
+    r = 2 * rng.integers(0, 1 << 11, (2, N))
+    cm_acc[4, 0] = RF.i32((OFF - r[0]) // 2)                    # -2 acc = -offset + r
+    cm_acc[4, 1] = RF.i32((OFF + (1 << 12) - r[1]) // 2)        # -2 acc = -offset - 2^12 + r
+    out["cm_acc"], out["cm_bara"] = cm_acc, cm_bara
+    RF.pack(out, "cm_out", list(pool.map(lambda c: R.blind_rotate(cm_acc[c], cm_bara[c]), range(8))), 5)
+
+    # (6) tfhe_blindRotateAndExtract, all 500 steps: the constant test vector and a table
+    # (T.lut_table over p = 8), each with barb = 0 and barb != 0; bara / barb are the reference's
+    # modSwitchFromTorus32 of the stored samples
+    f8 = np.array([3, 0, 7, 1, 6, 2, 5, 4])
+    tvs = np.stack([np.full(N, RF.MU, np.int32), T.lut_table(8, T.lut_encode(f8, 8))])
+    bre_tv = np.array([0, 0, 1, 1], np.int32)
+    bre_x_a = words(4, n)
+    bre_x_b = words(4)
+    bre_x_b[0], bre_x_b[2] = 0, 12345
+    bre_bara = np.stack([R.modswitch(v, 2 * N) for v in bre_x_a])
+    bre_barb = R.modswitch(bre_x_b, 2 * N)
+    assert bre_barb[0] == 0 and bre_barb[2] == 0 and bre_barb[1] != 0 and bre_barb[3] != 0
+    bre = list(pool.map(lambda c: R.blind_rotate_extract(tvs[bre_tv[c]], bre_barb[c], bre_bara[c]), range(4)))
+    out["bre_tvs"], out["bre_tv"], out["bre_x_a"], out["bre_x_b"] = tvs, bre_tv, bre_x_a, bre_x_b
+    out["bre_bara"], out["bre_barb"] = bre_bara, bre_barb
+    RF.pack(out, "bre_out_a", [e[0] for e in bre], 4)
+    out["bre_out_b"] = RF.i32([e[1] for e in bre])
+
+    # (6b) one blind rotation at log_nu = 4 (bara, barb multiples of 16), extracted at 0, 1, 15:
+    # the many-LUT form; the table's 16 x 8 words are all different
+    ml_vals = (np.arange(128, dtype=np.int64).reshape(16, 8) * 2 + 1) * 0x00FEDCBB
+    ml_tv = T.lut_table_many(8, ml_vals, 4)
+    ml_x_a, ml_x_b = words(n), int(words(1)[0])
+    ml_bara = 16 * R.modswitch(ml_x_a, 2 * N // 16)
+    ml_barb = 16 * int(R.modswitch([ml_x_b], 2 * N // 16)[0])
+    acc0 = np.zeros((2, N), np.int32)
+    acc0[1] = ml_tv if ml_barb == 0 else R.mul_by_xai(2 * N - ml_barb, ml_tv)
+    ml_acc = R.blind_rotate(acc0, ml_bara)
+    ml_index = np.array([0, 1, 15], np.int32)
+    ml = [R.extract(ml_acc, f) for f in ml_index]
+    out["ml_tv"], out["ml_x_a"], out["ml_x_b"], out["ml_index"] = ml_tv, ml_x_a, np.array(ml_x_b, np.int32), ml_index
+    RF.pack(out, "ml_out_a", [e[0] for e in ml], 3)
+    out["ml_out_b"] = RF.i32([e[1] for e in ml])
+
+    # (7) tfhe_bootstrap_woKS and tfhe_bootstrap: random inputs, the modswitch wrap edge
+    # x_b = -2^20 + 5, runs of mask words 0 and -2^20 (bara = 0: skipped steps)
+    bs_x_a = words(5, n)
+    bs_x_b = words(5)
+    bs_x_b[3] = -2**20 + 5
+    bs_x_a[4, :25] = 0
+    bs_x_a[4, 25:50] = -2**20
+    woks = list(pool.map(lambda c: R.bootstrap_woks(RF.MU, bs_x_a[c], bs_x_b[c]), range(5)))
+    boot = list(pool.map(lambda c: R.bootstrap(RF.MU, bs_x_a[c], bs_x_b[c]), range(5)))
+    out["bs_x_a"], out["bs_x_b"] = bs_x_a, bs_x_b
+    RF.pack(out, "bs_woks_a", [e[0] for e in woks], 5)
+    out["bs_woks_b"] = RF.i32([e[1] for e in woks])
+    RF.pack(out, "bs_full_a", [e[0] for e in boot], 5)
+    out["bs_full_b"] = RF.i32([e[1] for e in boot])
+
+    # (8) gates on fresh encryptions: 4 NAND, 4 XOR, 2 MUX (every input combination of the
+    # two-input gates; MUX with the selector 0 and 1)
+    code = np.array([RF.NAND] * 4 + [RF.XOR] * 4 + [RF.MUX] * 2, np.int32)
+    bits = np.array([[0, 0, 0], [0, 1, 0], [1, 0, 0], [1, 1, 0]] * 2 + [[0, 1, 0], [1, 0, 1]], np.int32)
+    g_a = np.zeros((10, 3, n), np.int32)
+    g_b = np.zeros((10, 3), np.int32)
+    for k in range(3):
+        g_a[:, k], g_b[:, k] = K.encrypt(bits[:, k], rng)
+    g_a[:8, 2], g_b[:8, 2] = 0, 0
+    gates = list(pool.map(lambda c: R.gate(code[c], g_a[c], g_b[c]), range(10)))
+    out["gate_code"], out["gate_bits"], out["gate_in_a"], out["gate_in_b"] = code, bits, g_a, g_b
+    RF.pack(out, "gate_out_a", [e[0] for e in gates], 10)
+    out["gate_out_b"] = RF.i32([e[1] for e in gates])
+
+    R.close()
+    K.close()
+    save_npz(RF.PATH, out)
+    size = os.path.getsize(RF.PATH)
+    print("wrote", RF.PATH, size, "bytes")
+    assert size < 1000000, "ref_hotpath_vectors.npz must stay under 1 MB"
+
+
 if __name__ == "__main__":
-    main()
+    what = sys.argv[1:] or ["leaf", "hotpath"]
+    if "leaf" in what:
+        main()
+    if "hotpath" in what:
+        hotpath()
