@@ -1,5 +1,7 @@
-// api_internal.h — constructors shared by the Tier-1 API (tfhe_api.cpp) and the key /
-// ciphertext file I/O (tfhe_io.cpp).  Not installed; the public surface is include/tfhe/.
+// api_internal.h — what the library's host modules share: constructors of the Tier-1 API's structs
+// (tfhe_api.cpp) for the key / ciphertext file I/O (tfhe_io.cpp), the seam between the API's
+// host-only half and its device half (tier1.cpp), and the engine's internal entry points.  Not
+// installed; the public surface is include/tfhe/.
 #pragma once
 
 #include <vector>
@@ -42,10 +44,22 @@ TGswKey *new_tgsw_key(const ParamsImpl *P);                  // zero key
 LweBootstrappingKey *new_bk(const ParamsImpl *P);            // zero BK + zero KSK
 LweBootstrappingKeyFFT *new_bkfft(const LweBootstrappingKey *bk);
 
+// tfhe_api.cpp <-> tier1.cpp, all that crosses between the two halves (within the library: not exported)
+#pragma GCC visibility push(hidden)
+// coefficient-domain block [kn][4][2][kN] of a bkFFT made by this library
+const int32_t *bk_coef_of(const LweBootstrappingKeyFFT *k);
+// flat [kN][8][4][kn+1] view of any LweKeySwitchKey (ours or foreign-built)
+void ksk_flatten(const LweKeySwitchKey *ks, int32_t *out);
+// the key that owns an element of a live TGswSampleFFT array and the element's index (null: not ours)
+const LweBootstrappingKeyFFT *gsw_key_of(const TGswSampleFFT *p, int *index);
+// tier1.cpp: destroys the device contexts registered for a bkFFT and its KSK (the key is being deleted)
+void forget_device_keys(const void *bkfft, const void *ks);
+#pragma GCC visibility pop
+
 }  // namespace api
 }  // namespace tfhe_amd
 
-// tfhe_api.cpp <-> multi.cpp (multi-device batches)
+// tfhe_api.cpp, tier1.cpp <-> multi.cpp (multi-device batches)
 // coefficient-domain bootstrapping key of a cloud key (int32 [500][4][2][1024])
 int tfhe_amd_internal_bk_coef(const TFheGateBootstrappingCloudKeySet *bk, int32_t *out);
 // one SoA batch of a gate on the key's Tier-1 device context (this thread's lane)
@@ -67,7 +81,7 @@ int tfhe_amd_internal_ks_variance(TfheAmdContext *c, int B, int halves, const do
 int tfhe_amd_internal_mixed_variance(TfheAmdContext *c, int B, const double *d_var, double *out);
 // Rows of an array of records that each point to their a[500] and hold b (and current_variance):
 // record i is at base + i * stride; its a pointer at a_off, b at b_off, current_variance at v_off
-// (tfhe_api.cpp: LweSample arrays, without the engine knowing the struct)
+// (tier1.cpp: LweSample arrays, without the engine knowing the struct)
 struct TfheAmdRows {
     char *base;
     size_t stride, a_off, b_off, v_off;

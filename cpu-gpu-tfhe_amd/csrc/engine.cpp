@@ -750,7 +750,7 @@ extern "C" int tfhe_amd_external_product_dev(TfheAmdContext *c, int B, const int
     return TFHE_AMD_OK;
 }
 
-// The L1 entry points of the TFHE API on host data (tfhe_api.cpp): op 0 = external product
+// The L1 entry points of the TFHE API on host data (tier1.cpp): op 0 = external product
 // (arg = key indices [B]), op 1 = tfhe_blindRotate_FFT (arg = bara [B][iters], the exact v4 CMux
 // steps, skipping a_i = 0 as lwe-bootstrapping-functions-fft.cu:705); acc [B][2][kN] in place.
 int tfhe_amd_internal_l1(TfheAmdContext *c, int op, int B, int iters, const int32_t *arg, int32_t *acc) {
@@ -794,7 +794,7 @@ int tfhe_amd_internal_device_cus(int device) {
     return n;
 }
 
-// device copy of host data on a context's GPU (tfhe_api.cpp: the KSK row variances)
+// device copy of host data on a context's GPU (tier1.cpp: the KSK row variances)
 int tfhe_amd_internal_upload(TfheAmdContext *c, const void *host, size_t bytes, void **dev) {
     if (!c || !host || !dev) return TFHE_AMD_E_ARG;
     DeviceScope dev_scope(c->device);

@@ -282,7 +282,7 @@ static int gate_batch_host_sliced(TfheAmdContext *c, int gate, int B, int32_t *r
     return slice_pipeline(c, gate, B, nin, stage_in, stage_out, nullptr, "sliced");
 }
 
-// Record batches (tfhe_api.cpp tfhe_amd_boots_batch over LweSample arrays).  The records' rows
+// Record batches (tier1.cpp tfhe_amd_boots_batch over LweSample arrays).  The records' rows
 // are gathered by the copy pool straight into the pinned staging buffer (no intermediate SoA copy)
 // and the results scattered back the same way, with each result's current_variance.
 static inline int32_t *rec_a(const TfheAmdRows &r, int i) {
@@ -802,13 +802,13 @@ extern "C" int tfhe_amd_bootstrap_lut_batch_host(TfheAmdContext *c, int B, int n
 // ------------------------------------------------------------------ read-backs of the last batch
 
 // largest batch the host path runs unsliced, i.e. whose key-switch inputs are all in the scratch
-// afterwards (tfhe_api.cpp's variance bookkeeping rounds)
+// afterwards (tier1.cpp's variance bookkeeping rounds)
 int tfhe_amd_internal_unsliced_max() { return host_slice(); }
 
 // The extracted samples (key-switch inputs) of this context's last gate batch of at most one
 // round (unsliced host path), halves x B rows of kN words: the Tier-1 API's per-thread-lane mode
 // (TFHE_AMD_TIER1_COALESCE=0) and raw tfhe_bootstrap_FFT derive the key-switched output's
-// current_variance from their digits (tfhe_api.cpp ks_variance).
+// current_variance from their digits (tier1.cpp ks_variance).
 int tfhe_amd_internal_last_extracted(TfheAmdContext *c, int B, int halves, int32_t *u_a) {
     if (!c || B <= 0 || halves < 1 || halves > 2 || (size_t)halves * B > 2 * (size_t)c->cap) return TFHE_AMD_E_ARG;
     EntryFrame f(c, 0, false);

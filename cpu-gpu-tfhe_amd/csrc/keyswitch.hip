@@ -580,7 +580,7 @@ hipError_t launch_ksk_to_v5(const int32_t *d_ksk, int32_t *d_ksk5, hipStream_t s
     return hipGetLastError();
 }
 
-// current_variance bookkeeping of B key-switched samples (tfhe_api.cpp tfhe_amd_boots_batch and the
+// current_variance bookkeeping of B key-switched samples (tier1.cpp tfhe_amd_boots_batch and the
 // Tier-1 queue): per sample the reference's sum over i < 1024, j < 8 of the variance of the
 // key-switching-key row its non-zero digit selects (lweKeySwitchTranslate_fromArray,
 // lwe-keyswitch-functions.cu:101-127; lwe-functions.cu:150), in the same i, j order with the same

@@ -365,7 +365,7 @@ extern "C" int tfhe_gpu_init(const TFheGateBootstrappingCloudKeySet *bk, int dev
     return TFHE_AMD_OK;
 }
 
-// drop the multi-context of a key being deleted (tfhe_api.cpp delete_* hooks)
+// drop the multi-context of a key being deleted (tfhe_api.cpp delete_* hooks, beside tier1.cpp's forget_device_keys)
 void tfhe_amd_internal_forget_multi(const void *bkfft) {
     std::shared_ptr<TfheAmdMulti> m;   // in-flight batches keep their own reference
     {

@@ -1,11 +1,12 @@
 """ThreadSanitizer run of the library's concurrency code (SURVEY.md §5 "race detection: TSan on the
 CPU build").
 
-tests/tsan builds csrc/tfhe_api.cpp (key registry, per-thread lanes, the two-lane Tier-1
-coalescing queue), csrc/multi.cpp (tfhe_gpu_init registry, per-device workers) and
-csrc/circuit.cpp (per-context device state) UNCHANGED with -fsanitize=thread against a CPU
-stand-in for the device engine (tests/tsan/stub_engine.cpp: the engine's locking discipline, a
-deterministic stand-in for the gate arithmetic) and for the HIP host API (tests/tsan/stub/).
+tests/tsan builds csrc/tier1.cpp (key registry, per-thread lanes, the two-lane Tier-1
+coalescing queue), csrc/multi.cpp (tfhe_gpu_init registry, per-device workers),
+csrc/circuit.cpp (per-context device state) and the engine under them (csrc/engine.cpp,
+csrc/host_batch.cpp) UNCHANGED with -fsanitize=thread; the stand-ins end at the kernel launchers
+(tests/tsan/stub_kernels.cpp: deterministic hashes for the gate arithmetic) and the HIP host API
+(tests/tsan/stub/).  Both drivers link the same objects.
 The driver hammers them: 64 threads of Tier-1 gate chains with results aliasing inputs and mixed
 gate kinds (the reference's OpenMP callers, cpuParallel/Cipher.cpp:83-120, cloud.cpp:389-395);
 tfhe_gpu_boots_batch from 8 threads on either device while tfhe_gpu_init re-registers the key and
@@ -14,10 +15,9 @@ that come and go.  Every result is compared word for word (current_variance bit 
 the same work done sequentially, and DeviceScope's save / restore logic is unit-tested with the
 stub's per-thread current device.  Pass = exit 0 and no ThreadSanitizer report.
 
-Round 5: csrc/engine.cpp and csrc/host_batch.cpp (the host-pointer paths)
-themselves are built the same way (tests/tsan/_bin/tsan_engine:
-the whole host library + CPU stand-in kernels, tests/tsan/stub_kernels.cpp) against a stub HIP
-runtime whose streams are asynchronous worker threads, so a host read that is not ordered after
+Round 5: the second driver (tests/tsan/_bin/tsan_engine) aims at
+csrc/engine.cpp and csrc/host_batch.cpp (the host-pointer paths) themselves.  The stub HIP
+runtime's streams are asynchronous worker threads, so a host read that is not ordered after
 the stream work producing it is a race TSan sees.  tsan_engine_driver.cpp hammers the host copy
 pool from three contexts (two devices, one a key replica built meanwhile), several threads on one
 context at once, over the staged, sliced, record (LweSample rows + device current_variance) and

@@ -1,5 +1,5 @@
 // Test-only stand-in for <hip/hip_runtime.h>: the host-side HIP API the library's host code calls
-// (csrc/engine.cpp, tfhe_api.cpp, multi.cpp, circuit.cpp, engine.h's DeviceScope / StreamFence),
+// (csrc/engine.cpp, host_batch.cpp, tier1.cpp, multi.cpp, circuit.cpp, engine.h's DeviceScope / StreamFence),
 // implemented on the CPU so that code can be built with -fsanitize=thread and no GPU
 // (tests/test_concurrency_tsan.py).  "Device memory" is host memory and the current device is per
 // thread, as in HIP.  Streams are ASYNCHRONOUS: each stream is a worker thread that runs its queue
@@ -122,6 +122,16 @@ inline StubStream *null_stream() {
     return s;
 }
 inline StubStream *of(hipStream_t s) { return s ? s : null_stream(); }
+// what is allocated and not yet given back (the drivers' end-of-run leak check); the null stream
+// lives as long as the process and is not counted
+inline std::atomic<long> &live_events() { static std::atomic<long> n{0}; return n; }
+inline std::atomic<long> &live_blocks() { static std::atomic<long> n{0}; return n; }
+struct Live { long streams, events, blocks; };
+inline Live live() {
+    StubStream *null = null_stream();
+    std::lock_guard<std::mutex> lk(reg_mu());
+    return Live{(long)(streams().size() - streams().count(null)), live_events().load(), live_blocks().load()};
+}
 // enqueue device work (the stand-in kernels use this too)
 inline void enqueue(hipStream_t s, std::function<void()> f) { of(s)->push(std::move(f)); }
 }  // namespace hip_stub
@@ -136,14 +146,22 @@ inline hipError_t hipSetDevice(int d) {
 }
 inline const char *hipGetErrorString(hipError_t) { return "stub"; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
-inline hipError_t hipMalloc(void **p, size_t n) { *p = calloc(1, n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+inline hipError_t hipMalloc(void **p, size_t n) {
+    *p = calloc(1, n ? n : 1);
+    if (*p) hip_stub::live_blocks()++;
+    return *p ? hipSuccess : hipErrorOutOfMemory;
+}
 template <class T> inline hipError_t hipMalloc(T **p, size_t n) { return hipMalloc((void **)p, n); }
-inline hipError_t hipFree(void *p) { free(p); return hipSuccess; }
+inline hipError_t hipFree(void *p) {
+    if (p) hip_stub::live_blocks()--;
+    free(p);
+    return hipSuccess;
+}
 inline hipError_t hipHostMalloc(void **p, size_t n, unsigned) { return hipMalloc(p, n); }
 template <class T> inline hipError_t hipHostMalloc(T **p, size_t n, unsigned f) { return hipHostMalloc((void **)p, n, f); }
 // host memory is the device's in the stand-in: mapped at the same address
 inline hipError_t hipHostGetDevicePointer(void **dp, void *p, unsigned) { *dp = p; return hipSuccess; }
-inline hipError_t hipHostFree(void *p) { free(p); return hipSuccess; }
+inline hipError_t hipHostFree(void *p) { return hipFree(p); }
 inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind) { if (n) memmove(d, s, n); return hipSuccess; }
 inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind, hipStream_t st) {
     if (n) hip_stub::enqueue(st, [=] { memmove(d, s, n); });
@@ -185,9 +203,17 @@ inline hipError_t hipDeviceSynchronize() {
         if (s->device == hip_stub::current()) s->drain();
     return hipSuccess;
 }
-inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { *e = new StubEvent(); return hipSuccess; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) {
+    *e = new StubEvent();
+    hip_stub::live_events()++;
+    return hipSuccess;
+}
 inline hipError_t hipEventCreate(hipEvent_t *e) { return hipEventCreateWithFlags(e, 0); }
-inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+inline hipError_t hipEventDestroy(hipEvent_t e) {
+    if (e) hip_stub::live_events()--;
+    delete e;
+    return hipSuccess;
+}
 inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t st) {
     uint64_t t;
     {

@@ -1,8 +1,9 @@
 // ThreadSanitizer driver for the library's concurrency code (tests/test_concurrency_tsan.py):
-// tfhe_api.cpp (key registry, per-thread lanes, the two-lane Tier-1 coalescing queue),
+// tier1.cpp (key registry, per-thread lanes, the two-lane Tier-1 coalescing queue),
 // multi.cpp (tfhe_gpu_init registry, per-device workers) and circuit.cpp (per-context device
-// state, dropped with its context) built with -fsanitize=thread against the CPU stand-in engine
-// (stub_engine.cpp) and the HIP stand-in header (stub/hip/hip_runtime.h).  Every phase compares
+// state, dropped with its context) built with -fsanitize=thread on the engine itself (engine.cpp,
+// host_batch.cpp) against the stand-in kernels (stub_kernels.cpp) and the asynchronous stub HIP
+// runtime (stub/hip/hip_runtime.h).  Every phase compares
 // its concurrent results word for word (and current_variance bit for bit) with the same work run
 // sequentially.  Exit 0 = all equal; ThreadSanitizer itself exits 66 on any report.
 // Reference callers whose concurrency this models: cpuParallel/Cipher.cpp:83-120 (OpenMP gate
@@ -23,9 +24,6 @@
 #include "../../include/tfhe/tfhe_io.h"
 #include "../../include/tfhe_amd.h"
 
-extern "C" long stub_live_contexts();
-extern "C" long stub_set_device_calls();
-
 static int g_fail = 0;
 #define CHECK(cond, ...)                                    \
     do {                                                    \
@@ -42,7 +40,7 @@ using tfhe_amd::DeviceScope;
 // ---- DeviceScope (engine.h): save / switch / restore, nesting, no-op cases
 static void test_device_scope() {
     hipSetDevice(1);
-    const long calls0 = stub_set_device_calls();
+    const long calls0 = hip_stub::set_calls();
     {
         DeviceScope a(0);
         int d = -1;
@@ -66,7 +64,7 @@ static void test_device_scope() {
     hipGetDevice(&d);
     CHECK(d == 1, "caller's device restored: current %d", d);
     // 3 switches: into 0, into nested 1, back to 0 (nested restore), back to 1 (outer restore)
-    CHECK(stub_set_device_calls() - calls0 == 4, "hipSetDevice calls %ld", stub_set_device_calls() - calls0);
+    CHECK(hip_stub::set_calls() - calls0 == 4, "hipSetDevice calls %ld", hip_stub::set_calls() - calls0);
     {
         DeviceScope bad(7);   // a device that does not exist: rc reports it, nothing changes
         hipGetDevice(&d);
@@ -290,7 +288,9 @@ static void test_circuits(const TFheGateBootstrappingCloudKeySet *bk, int thread
     {
         TfheAmdContext *c0 = nullptr;
         tfhe_amd_context_create(bk, 0, &c0);
-        CHECK(tfhe_amd_circuit_run_dev(c0, C, B, want_a.data(), want_b.data(), nullptr) == 0, "circuit run");
+        // tfhe_amd_circuit_run_dev enqueues and returns: the wires are read after tfhe_amd_sync
+        CHECK(tfhe_amd_circuit_run_dev(c0, C, B, want_a.data(), want_b.data(), nullptr) == 0 &&
+                  tfhe_amd_sync(c0) == 0, "circuit run");
         tfhe_amd_context_destroy(c0);
     }
     CHECK(tfhe_amd_circuit_state_count(C) == 0, "state dropped with its context: %d left",
@@ -303,8 +303,8 @@ static void test_circuits(const TFheGateBootstrappingCloudKeySet *bk, int thread
                 TfheAmdContext *c = nullptr;
                 if (tfhe_amd_context_create(bk, t & 1, &c) != 0) { bad++; continue; }
                 std::vector<int32_t> wa = wa0, wb = wb0;
-                if (tfhe_amd_circuit_run_dev(c, C, B, wa.data(), wb.data(), nullptr) != 0 || wa != want_a ||
-                    wb != want_b)
+                if (tfhe_amd_circuit_run_dev(c, C, B, wa.data(), wb.data(), nullptr) != 0 || tfhe_amd_sync(c) != 0 ||
+                    wa != want_a || wb != want_b)
                     bad++;
                 tfhe_amd_context_destroy(c);
             }
@@ -336,7 +336,9 @@ int main(int argc, char **argv) {
     test_circuits(bk, 8);
     delete_gate_bootstrapping_secret_keyset(key);
     delete_gate_bootstrapping_parameters(params);
-    CHECK(stub_live_contexts() == 0, "%ld contexts leaked", stub_live_contexts());
+    const hip_stub::Live left = hip_stub::live();   // every context, lane and worker gave its own back
+    CHECK(left.streams == 0 && left.events == 0 && left.blocks == 0, "%ld streams, %ld events, %ld blocks leaked",
+          left.streams, left.events, left.blocks);
     printf(g_fail ? "tsan_driver: FAILED\n" : "tsan_driver: ok\n");
     return g_fail;
 }
