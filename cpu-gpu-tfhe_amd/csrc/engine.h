@@ -216,6 +216,14 @@ hipError_t launch_tgsw_cmux_v4(const DeviceKey &key, const uint32_t *set, int pa
 hipError_t launch_tgsw_to_ntt(const int32_t *d_coef, uint32_t *d_ntt, const NttTables *d_tab, int count,
                               hipStream_t s);
 hipError_t launch_tgsw_v1_to_v2(const uint32_t *d_v1, uint32_t *d_v2, int count, hipStream_t s);
+// ---- LWE -> TLWE packing key switch (pack.cpp, pack_v4.hip).  pack_key: the 750 row
+// groups in the bk_v2 layout; dig: scratch of T * kn * kN words.  T <= kPackMaxBatch outputs of P
+// inputs each, in_a [T][P][kn], in_b [T][P], pos [P] (null: pos[p] = p), out [T][2][kN].  Two
+// launches, k_pack_digits and k_pack_v4; G > 1 splits the key rows of each output over G workgroups
+// ("k_pack_v4(split)").  pack_split: the G the entry points use for T outputs on `cus` compute units.
+int pack_split(int T, int cus);
+hipError_t launch_pack(const DeviceKey &key, const uint32_t *pack_key, int T, int P, const int32_t *in_a,
+                       const int32_t *in_b, const int32_t *pos, uint32_t *dig, int G, int32_t *out, hipStream_t s);
 // circuit level (v4 kernel): B instances x nrows rows, wires [W][B] ciphertexts, u slots r B + k
 hipError_t launch_blind_rotate_v4_rows(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,

@@ -21,6 +21,16 @@ constexpr uint32_t kDecompOffset = 512u * ((1u << 22) + (1u << 12));   // 214958
 constexpr uint32_t kKsPrecOffset = 1u << (32 - (1 + kKsBasebit * kKsT)); // 2^15
 // current_variance tables (k_ks_variance): the KSK row variances [kN][kKsT][kKsBase], then a flag
 // (non-zero: every row has the same variance), then the sequential sums of k copies, k <= kN kKsT
+// LWE -> TLWE packing key switch: base 2^4, t = 6 balanced digits in [-8, 7] (24 bits
+// of a mask word): with u = a + kPackOffset, d_j(a) = ((u >> (32 - 4 j)) & 15) - 8, j = 1 .. 6, and
+// sum_j d_j 2^(32 - 4 j) differs from a by at most 2^7; a = 0 has all-zero digits.
+constexpr int kPackBasebit = 4;
+constexpr int kPackT = 6;
+constexpr uint32_t kPackOffset = 0x88888880u;   // sum_j 8 * 2^(32 - 4 j) + 2^7
+constexpr int kPackRows = kn * kPackT;          // key rows (i, j), each a TLWE sample [2][kN]
+constexpr int kPackGroups = kPackRows / 4;      // 750 groups in the shape of a TGSW sample
+constexpr int kPackUnits = kPackRows / 12;      // 250 units of two key bits (pack_v4.hip)
+constexpr int kPackMaxBatch = 512;              // outputs per launch pair (2 MB of digit scratch each)
 constexpr int kKsVarUniform = kN * kKsT * kKsBase;
 constexpr int kKsVarWords = kKsVarUniform + 1 + kN * kKsT + 1;
 

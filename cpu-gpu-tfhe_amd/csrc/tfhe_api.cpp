@@ -507,6 +507,43 @@ EXPORT int tfhe_amd_tlwe_encrypt_polys(const TFheGateBootstrappingSecretKeySet *
     return TFHE_AMD_OK;
 }
 
+// ---- client side of the packing key switch (include/tfhe_amd.h).  Row (i, j) of the
+// key, j = 1 .. kPackT: a zero row under the keyset's TLWE key at its alpha_min (the loop above)
+// plus the constant polynomial s_i 2^(32 - 4 j) on b; out [kn][kPackT][2: a, b][kN], rows drawn in
+// (i, j) order.
+EXPORT int tfhe_amd_pack_key_generate(const TFheGateBootstrappingSecretKeySet *key, int32_t *out) {
+    if (!key || !key->tgsw_key || !key->lwe_key || !out) return TFHE_AMD_E_ARG;
+    const TGswKey *gk = key->tgsw_key;
+    const double alpha = gk->tlwe_params->alpha_min;
+    const int *coefs = gk->tlwe_key.key[0].coefs;
+    std::lock_guard<std::mutex> lk(g_rng_mu);
+    for (int i = 0; i < kn; ++i)
+        for (int j = 1; j <= kPackT; ++j) {
+            uint32_t *r = (uint32_t *)out + ((size_t)i * kPackT + (j - 1)) * 2 * kN;
+            tlwe_zero_rows_nolock(r, r + kN, alpha, coefs);
+            r[kN] += (uint32_t)key->lwe_key->key[i] << (32 - kPackBasebit * j);
+        }
+    return TFHE_AMD_OK;
+}
+
+// in [n][2: a, b][kN] -> phase [n][kN] = b - a s mod 2^32 under the keyset's TLWE key (negacyclic)
+EXPORT int tfhe_amd_tlwe_phase_polys(const TFheGateBootstrappingSecretKeySet *key, int n, const int32_t *in,
+                                     int32_t *phase) {
+    if (!key || !key->tgsw_key || n < 0 || !in || !phase) return TFHE_AMD_E_ARG;
+    const int *coefs = key->tgsw_key->tlwe_key.key[0].coefs;
+    for (int k = 0; k < n; ++k) {
+        const uint32_t *a = (const uint32_t *)in + (size_t)k * 2 * kN, *b = a + kN;
+        uint32_t *ph = (uint32_t *)phase + (size_t)k * kN;
+        for (int j = 0; j < kN; ++j) ph[j] = b[j];
+        for (int s = 0; s < kN; ++s) {
+            if (!coefs[s]) continue;         // ph -= X^s * a (negacyclic)
+            for (int i = 0; i < s; ++i) ph[i] += a[i - s + kN];
+            for (int i = s; i < kN; ++i) ph[i] -= a[i - s];
+        }
+    }
+    return TFHE_AMD_OK;
+}
+
 EXPORT TFheGateBootstrappingSecretKeySet *
 new_random_gate_bootstrapping_secret_keyset(const TFheGateBootstrappingParameterSet *params) {
     const ParamsImpl *P = params_of(params);

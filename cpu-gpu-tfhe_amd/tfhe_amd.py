@@ -24,6 +24,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TFHE_AMD_LIB") or os.path.join(HERE, "lib", "libtfhe_amd.so")
 
 N, n_lwe, KPL, KS_T, KS_BASE = 1024, 500, 4, 8, 4
+PACK_T = 6   # digits of the packing key switch (params.h kPackT)
 GATES = {"NAND": 0, "OR": 1, "AND": 2, "XOR": 3, "XNOR": 4, "NOR": 5,
          "ANDNY": 6, "ANDYN": 7, "ORNY": 8, "ORYN": 9, "MUX": 10}
 MU = 1 << 29   # modSwitchToTorus32(1, 8)
@@ -148,6 +149,13 @@ def _load():
     for f in ("tfhe_amd_tgsw_lookup_woks_host", "tfhe_amd_tgsw_lookup_host"):
         getattr(L, f).argtypes = ([_VP, _VP, ctypes.c_int, ctypes.c_int, _I32P] + [ctypes.c_int] * 3 + [_I32P, _I32P]
                                   + [ctypes.c_int] * 2 + [_I32P, _I32P])
+    # packing key switch (tfhe_amd_pack_*)
+    L.tfhe_amd_pack_key_generate.argtypes = [_VP, _I32P]
+    L.tfhe_amd_tlwe_phase_polys.argtypes = [_VP, ctypes.c_int, _I32P, _I32P]
+    L.tfhe_amd_pack_key_import.argtypes = [_VP, _I32P, ctypes.POINTER(_VP)]
+    L.tfhe_amd_pack_key_destroy.argtypes = [_VP]
+    L.tfhe_amd_pack_dev.argtypes = [_VP, _VP, ctypes.c_int, ctypes.c_int] + [_VP] * 4 + [_VP]
+    L.tfhe_amd_pack_host.argtypes = [_VP, _VP, ctypes.c_int, ctypes.c_int] + [_I32P] * 4
     return L
 
 
@@ -493,6 +501,22 @@ class SecretKeyset:
         _check(lib.tfhe_amd_tlwe_encrypt_polys(self.h, mu.shape[0], _p(mu), _p(out)), "tlwe_encrypt_polys")
         return out
 
+    # ---- client side of the packing key switch (tfhe_amd_pack_*)
+    def pack_key(self):
+        """tfhe_amd_pack_key_generate: the LWE -> TLWE packing key [500][6][2][1024]
+        (Context.pack_key_import takes it)"""
+        out = np.zeros((n_lwe, PACK_T, 2, N), np.int32)
+        _check(lib.tfhe_amd_pack_key_generate(self.h, _p(out)), "pack_key_generate")
+        return out
+
+    def tlwe_phase(self, polys):
+        """tfhe_amd_tlwe_phase_polys: TLWE samples [n][2][1024] (or one [2][1024]) -> phases
+        b - a s [n][1024] under the keyset's TLWE key"""
+        x = i32(polys).reshape(-1, 2, N)
+        out = np.zeros((x.shape[0], N), np.int32)
+        _check(lib.tfhe_amd_tlwe_phase_polys(self.h, x.shape[0], _p(x), _p(out)), "tlwe_phase_polys")
+        return out
+
 
 class CloudKeyset:
     """new_tfheGateBootstrappingCloudKeySet_fromFile (tfhe_io.cu:1117): what cloud.cpp loads."""
@@ -539,6 +563,25 @@ class TgswSet:
     def close(self):
         if getattr(self, "h", None):
             lib.tfhe_amd_tgsw_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PackKey:
+    """TfheAmdPackKey: the packing key imported to a context's device (Context.pack_key_import);
+    close() frees it.  It does not depend on the context's lifetime."""
+
+    def __init__(self, h, device):
+        self.h, self.device = h, device
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.tfhe_amd_pack_key_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -868,6 +911,46 @@ class Context:
                                                 tab.data_ptr(), None if tab_index is None else tab_index.data_ptr(),
                                                 int(log_stride), n_out, out_a.data_ptr(), out_b.data_ptr(), stream),
                name)
+
+    # ---- packing key switch (tfhe_amd_pack_*): computed LWE samples -> TLWE ciphertexts
+    def pack_key_import(self, coef):
+        """tfhe_amd_pack_key_import: coef [500][6][2][1024] (SecretKeyset.pack_key) -> PackKey on this
+        context's device"""
+        coef = i32(coef)
+        if coef.shape != (n_lwe, PACK_T, 2, N):
+            raise TfheAmdError(f"coef: need int32 [500][6][2][1024], got {coef.shape}")
+        h = _VP()
+        _check(lib.tfhe_amd_pack_key_import(self.h, _p(coef), ctypes.byref(h)), "pack_key_import")
+        return PackKey(h.value, self.device)
+
+    def pack_host(self, pkey, in_a, in_b, pos=None):
+        """tfhe_amd_pack_host: in_a [T][P][500], in_b [T][P] (or one output's [P][500], [P]), pos [P]
+        distinct positions (None: 0 .. P - 1) -> TLWE ciphertexts [T][2][1024]"""
+        in_a = i32(in_a); in_b = i32(in_b)
+        if in_a.ndim == 2:
+            in_a, in_b = in_a[None], in_b[None]
+        if in_a.ndim != 3 or in_a.shape[2] != n_lwe or in_b.shape != in_a.shape[:2]:
+            raise TfheAmdError(f"need in_a [T][P][500] and in_b [T][P], got {in_a.shape}, {in_b.shape}")
+        T_, P = in_b.shape
+        pos = None if pos is None else i32(pos)
+        if pos is not None and pos.shape != (P,):
+            raise TfheAmdError(f"pos: need one position per input ({P}), got {pos.shape}")
+        out = np.zeros((T_, 2, N), np.int32)
+        _check(lib.tfhe_amd_pack_host(self.h, pkey.h, T_, P, _p(in_a), _p(in_b), _p(pos), _p(out)), "pack_host")
+        return out
+
+    def pack_dev(self, pkey, in_a, in_b, out, pos=None, stream=None):
+        """tfhe_amd_pack_dev on torch tensors (shapes as pack_host, out [T][2][1024]); asynchronous"""
+        if in_b is None or in_b.dim() != 2:
+            raise TfheAmdError("need GPU tensors in_a [T][P][500] and in_b [T][P]")
+        T_, P = in_b.shape
+        named = [("in_a", in_a, (T_, P, n_lwe)), ("in_b", in_b, (T_, P)), ("out", out, (T_, 2, N))]
+        if pos is not None:
+            named.append(("pos", pos, (P,)))
+        for name, t, shape in named:
+            self._dev_check(t, shape, name)
+        _check(lib.tfhe_amd_pack_dev(self.h, pkey.h, T_, P, in_a.data_ptr(), in_b.data_ptr(),
+                                     None if pos is None else pos.data_ptr(), out.data_ptr(), stream), "pack_dev")
 
     def blind_rotate_dev(self, acc, bara, iters, stream=None):
         B = acc.shape[0]

@@ -289,6 +289,9 @@ int tfhe_amd_external_product_dev(TfheAmdContext *ctx, int B, const int32_t *key
  * LIMIT: the address bits must arrive as TGSW ciphertexts from the client.  A computed LWE bit
  * cannot be turned into one (that is circuit bootstrapping, which this library does not have), so
  * this serves the input layer of a computation: S-boxes, ROMs, private reads on client indices.
+ * The TABLE has no such limit: besides a plaintext polynomial or a client's encryption
+ * (tfhe_amd_tlwe_encrypt_polys) an encrypted table can come from tfhe_amd_pack_* below, which gathers
+ * up to 1024 computed LWE samples into one TLWE ciphertext on the device.
  *
  * Client side (host only, no GPU; both draw from the library's generator, so
  * tfhe_random_generator_setSeed makes them reproducible):
@@ -366,6 +369,60 @@ int tfhe_amd_tgsw_lookup_host(TfheAmdContext *ctx, TfheAmdTgsw *set, int B, int 
                               int n_tab, int n_poly, int tab_rows, const int32_t *tab,
                               const int32_t *tab_index, int log_stride, int n_out,
                               int32_t *res_a, int32_t *res_b);
+
+/* ---- Packing key switch: computed LWE samples gathered into TLWE ciphertexts.
+ * The public functional key switch with f = identity onto coefficient positions: P <= 1024 samples
+ * (a_p, b_p) under the n = 500 LWE key become ONE TLWE ciphertext under the keyset's TLWE key whose
+ * phase b - a s has, at coefficient pos[p], the phase of input p plus noise, and 0 plus noise at
+ * every unoccupied coefficient.  Two uses: a table for tfhe_amd_tgsw_lookup_* (tab_rows = 2) made of
+ * values the server computed, and result compression (1024 results in one 8 KB ciphertext that the
+ * client reads with one phase computation).  Arithmetic: base 2^4, 6 balanced digits in [-8, 7] of
+ * every mask word (24 bits), OUT = (0, sum_p b_p X^pos[p]) - sum_{i,j} D_ij (*) K_ij with
+ * D_ij = sum_p d_j(a_p[i]) X^pos[p], exact mod 2^32.  The added noise has the standard deviation
+ * sqrt(500 * 6 * 21.5 * P) * 7.18e-9 of the torus, 5.8e-5 at P = 1024.
+ *
+ * Client side (host only, no GPU):
+ * tfhe_amd_pack_key_generate: the key, int32 [500][6][2][1024] (24.6 MB): row (i, j) is a TLWE
+ *   encryption (a, then b) of the constant polynomial s_i 2^(32 - 4 j), j = 1 .. 6, under the
+ *   keyset's TLWE key at its alpha_min.  It draws from the library's generator, rows in (i, j)
+ *   order, so tfhe_random_generator_setSeed makes it reproducible.
+ * tfhe_amd_tlwe_phase_polys: phase [n][1024] = b - a s mod 2^32 of n TLWE samples in [n][2][1024]:
+ *   the client's read of packed results.
+ * Both return TFHE_AMD_E_ARG for a null pointer and for n < 0. */
+int tfhe_amd_pack_key_generate(const TFheGateBootstrappingSecretKeySet *key, int32_t *out);
+int tfhe_amd_tlwe_phase_polys(const TFheGateBootstrappingSecretKeySet *key, int n, const int32_t *in,
+                              int32_t *phase);
+
+/* The imported key: uploaded to the context's device and converted there into the exact kernels'
+ * layout (48 MB).  Synchronous.  Like a TfheAmdTgsw it lives on that device, does not depend on the
+ * context's lifetime and may be used with any context on the same device; pairing it with a
+ * context on another device returns TFHE_AMD_E_ARG.  It owns the digit scratch of the pack calls
+ * (2 MB per output of the largest batch so far, at most 512 outputs' worth; grown on demand).
+ * Destroy waits for the device. */
+typedef struct TfheAmdPackKey TfheAmdPackKey;
+int tfhe_amd_pack_key_import(TfheAmdContext *ctx, const int32_t *coef_host, TfheAmdPackKey **out);
+int tfhe_amd_pack_key_destroy(TfheAmdPackKey *key);
+
+/* T output ciphertexts of P inputs each: in_a [T][P][500], in_b [T][P], out [T][2][1024] (a, then
+ * b); pos [P] (shared by the T outputs; NULL: pos[p] = p) gives the distinct coefficient positions.
+ * A function-major many-LUT result [n_out][B][500] or a gate batch packs in place with T = n_out,
+ * P = B.  tfhe_amd_pack_dev takes device arrays and is asynchronous on `stream`; tfhe_amd_pack_host
+ * takes host arrays, stages through temporary device buffers and is synchronous.
+ * TFHE_AMD_E_ARG for T < 0, P outside [1, 1024] with T > 0, a null array, a null key or context and
+ * a context on another device than the key's; T = 0 returns TFHE_AMD_OK.  The host form also
+ * refuses a pos entry outside [0, 1024) and duplicate positions, and writes no output then.  The
+ * device form checks every pos entry on the device before any address is formed from it: an entry
+ * outside [0, 1024) drops that input (for the whole launch alike); duplicate positions are the
+ * caller's error and leave that output ciphertext unspecified, with nothing read or written out of
+ * bounds.
+ * There is no fp64 form: tfhe_amd_select_kernel and the exactness guard do not apply, the
+ * arithmetic is always the exact two-prime NTT.  tfhe_amd_last_kernels reports "k_pack_digits" and
+ * then "k_pack_v4(split)" when each output's key rows are split over several workgroups (T at most
+ * the device's compute units), else "k_pack_v4". */
+int tfhe_amd_pack_dev(TfheAmdContext *ctx, TfheAmdPackKey *key, int T, int P, const int32_t *in_a,
+                      const int32_t *in_b, const int32_t *pos, int32_t *out, void *stream);
+int tfhe_amd_pack_host(TfheAmdContext *ctx, TfheAmdPackKey *key, int T, int P, const int32_t *in_a,
+                       const int32_t *in_b, const int32_t *pos, int32_t *out);
 
 /* Timing of the engine's own kernels (HIP events on the stream they run on):
  * enable=1 starts accumulating; read returns the summed ms and launch counts of the
