@@ -152,17 +152,26 @@ __device__ __forceinline__ void cmux_v4(V4Shared &sh, const V4Args &g, int i, in
 // in device memory; tv = null (a constant row beside LUT rows) keeps the constant (mu, ..., mu)
 // MANY (many-LUT bootstrap; implies LUT): the modulus switch to a multiple of
 // 2^mo.th and the extraction of the coefficients 0 .. mo.n_out - 1 (modarith.h ManyOut)
-template <bool LUT = false, bool MANY = false>
+// TLWE (bootstrap from an encrypted accumulator; excludes LUT and MANY): the
+// accumulator starts from X^{2N - barb} (acc_a, acc_b), the TLWE sample at acc_src [2][kN]
+template <bool LUT = false, bool MANY = false, bool TLWE = false>
 __device__ __forceinline__ void br_v4_body(V4Shared &sh, const V4Args &g, const RowTerms &t, int32_t mu,
                                            int32_t *__restrict__ ua, int32_t *__restrict__ ub,
                                            const int32_t *__restrict__ tv = nullptr,
-                                           const ManyOut &mo = ManyOut{}) {
+                                           const ManyOut &mo = ManyOut{},
+                                           const int32_t *__restrict__ acc_src = nullptr) {
     const int tid = threadIdx.x;
     const int s = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = tid & 63;
     br_prologue<MANY, kV4Threads>(t, mo.th, tid, sh.bara, sh.barb);
     __syncthreads();
-    if (LUT && tv) {   // ACC = (0, X^{2N - barb} tv) as its periodic extension (modarith.h lut_coeff)
+    if constexpr (TLWE) {   // both rows of the periodic extension from the sample (modarith.h lut_coeff)
+        const int e = (k2N - sh.barb) & (k2N - 1);
+        for (int k = tid; k < kExt; k += kV4Threads) {
+            sh.E[0][k] = lut_coeff(acc_src, k, e);
+            sh.E[1][k] = lut_coeff(acc_src + kN, k, e);
+        }
+    } else if (LUT && tv) {   // ACC = (0, X^{2N - barb} tv) as its periodic extension (modarith.h lut_coeff)
         const int e = (k2N - sh.barb) & (k2N - 1);
         for (int k = tid; k < kExt; k += kV4Threads) {
             sh.E[0][k] = 0;
@@ -216,7 +225,7 @@ __device__ __forceinline__ bool guard_skip(const V4Guard &gd, size_t slot) {
 // (tfhe_amd_select_kernel(4): 256 VGPRs, 27 spilled), 1 for the guard launch (284 VGPRs, no scratch: a
 // kernel with a private segment costs ~12 us more per dispatch even when every workgroup exits
 // at once)
-template <int MINW, bool LUT = false, bool MANY = false>
+template <int MINW, bool LUT = false, bool MANY = false, bool TLWE = false>
 __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4(V4Args g, int B, int total, BrInput in0,
                                                                 BrInput in1, int32_t mu,
                                                                 int32_t *__restrict__ u_a,
@@ -233,7 +242,8 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4(V4Args g, 
         RowTerms t;
         row_terms<LUT>(t, in, idx);
         const LutArgs l = lut_args<LUT, MANY>(in, B, idx, gct, u_a, u_b);
-        br_v4_body<LUT, MANY>(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, l.tv, l.mo);
+        br_v4_body<LUT, MANY, TLWE>(sh, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, l.tv, l.mo,
+                                    acc_sample<TLWE>(in, idx));
     }
 }
 
@@ -458,7 +468,7 @@ hipError_t launch_blind_rotate_v4(const DeviceKey &key, int B, int halves, const
     with_mode(mode, [&](auto m) {
         with_flag(gd.flags != nullptr, [&](auto f) {
             hipLaunchKernelGGL((k_blind_rotate_v4<decltype(f)::value ? 1 : 2, mode_lut(decltype(m)::value),
-                                                  mode_many(decltype(m)::value)>),
+                                                  mode_many(decltype(m)::value), mode_tlwe(decltype(m)::value)>),
                                dim3(grid), dim3(kV4Threads), 0, s, v4_args(key), B, total, in[0], in1, mu, u_a, u_b, gd);
         });
     });
@@ -469,7 +479,7 @@ hipError_t launch_blind_rotate_v4_rows(const DeviceKey &key, int B, int nrows, c
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
                                        BrMode mode, const Guard *guard) {
     if (B <= 0 || nrows <= 0) return hipSuccess;
-    if (!key.bk_v2) return hipErrorInvalidValue;
+    if (!key.bk_v2 || mode == BrMode::Tlwe) return hipErrorInvalidValue;   // no rows form of the tlwe mode
     const V4Guard gd = v4_guard(guard);
     const long total = (long)B * nrows;
     const long grid = gd.flags && total > kGuardGrid ? kGuardGrid : total < 0x7fffffffL ? total : 0x7fffffffL;

@@ -372,11 +372,15 @@ __device__ __forceinline__ void cmux_v6(V6Ct &sh, const double2 *shtw, const V6A
 // MANY (many-LUT bootstrap; implies LUT): the prologue switches to a multiple of
 // 2^mo.th and the epilogue extracts the coefficients 0 .. mo.n_out - 1 (modarith.h ManyOut); the
 // 500 steps between them are the same.
-template <int WAVES, bool RREG, int C = 1, bool PS = false, bool LUT = false, bool MANY = false>
+// TLWE (bootstrap from an encrypted accumulator; excludes LUT and MANY): the
+// accumulator starts from X^{2N - barb} (acc_a, acc_b), the TLWE sample at acc_src [2][kN]: both
+// waves load their polynomial through lut_coeff, wave 0 the a part that otherwise starts as zero.
+template <int WAVES, bool RREG, int C = 1, bool PS = false, bool LUT = false, bool MANY = false, bool TLWE = false>
 __device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args &g, const RowTerms &t, int32_t mu,
                                            int32_t *__restrict__ ua, int32_t *__restrict__ ub, size_t slot,
                                            bool live = true, const int32_t *__restrict__ tv = nullptr,
-                                           const ManyOut &mo = ManyOut{}) {
+                                           const ManyOut &mo = ManyOut{},
+                                           const int32_t *__restrict__ acc_src = nullptr) {
     const int tid = threadIdx.x & (kV6Threads - 1);
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int L = tid & 63;
@@ -396,7 +400,12 @@ __device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args
     __syncthreads();
     // ACC = (0, X^{2N - barb} (mu, ..., mu)) (:1427-1431)
     uint32_t acc[16];
-    if (LUT && tv) {
+    if constexpr (TLWE) {
+        const int e = (k2N - sh.barb) & (k2N - 1);
+        const int32_t *src = acc_src + (size_t)w * kN;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = lut_coeff(src, L + 64 * r, e);
+    } else if (LUT && tv) {
         // ACC = (0, X^{2N - barb} tv) (modarith.h lut_coeff): wave 1 makes 16 loads per lane (64
         // consecutive words per load, up to the wrap), wave 0 stays zero
         const int e = (k2N - sh.barb) & (k2N - 1);
@@ -485,7 +494,7 @@ __device__ __forceinline__ void br_v6_body(V6Ct &sh, double2 *shtw, const V6Args
 #endif
 }
 
-template <int WAVES, bool RREG, bool LUT = false, bool MANY = false>
+template <int WAVES, bool RREG, bool LUT = false, bool MANY = false, bool TLWE = false>
 __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6(V6Args g, int B, int base, BrInput in0,
                                                                 BrInput in1, int32_t mu, int32_t *__restrict__ u_a,
                                                                 int32_t *__restrict__ u_b) {
@@ -497,14 +506,14 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6(V6Args g,
     RowTerms t;
     row_terms<LUT>(t, in, idx);
     const LutArgs l = lut_args<LUT, MANY>(in, B, idx, gct, u_a, u_b);
-    br_v6_body<WAVES, RREG, 1, false, LUT, MANY>(sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct,
-                                                 (size_t)gct, true, l.tv, l.mo);
+    br_v6_body<WAVES, RREG, 1, false, LUT, MANY, TLWE>(sh.ct[0], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct,
+                                                       (size_t)gct, true, l.tv, l.mo, acc_sample<TLWE>(in, idx));
 }
 
 // two ciphertexts per workgroup (4 waves): the dispatcher spreads a 4-wave workgroup over the
 // CU's 4 SIMDs, where two 2-wave workgroups sharing a CU land on 3 of them (2, 1, 1, 0 waves;
 // scripts/wave_placement.hip), so at B <= 2 CUs this keeps one wave per SIMD
-template <int WAVES, bool PS = false, bool LUT = false, bool MANY = false>
+template <int WAVES, bool PS = false, bool LUT = false, bool MANY = false, bool TLWE = false>
 __global__ __launch_bounds__(2 * kV6Threads, WAVES) void k_blind_rotate_v6p(V6Args g, int B, int total, int base,
                                                                      BrInput in0, BrInput in1, int32_t mu,
                                                                      int32_t *__restrict__ u_a,
@@ -521,8 +530,8 @@ __global__ __launch_bounds__(2 * kV6Threads, WAVES) void k_blind_rotate_v6p(V6Ar
     row_terms<LUT>(t, in, idx);
     // (the padding ciphertext repeats the last live one, table included)
     const LutArgs l = lut_args<LUT, MANY>(in, B, idx, gct, u_a, u_b);
-    br_v6_body<WAVES, true, 2, PS, LUT, MANY>(sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct, (size_t)gct,
-                                              live, l.tv, l.mo);
+    br_v6_body<WAVES, true, 2, PS, LUT, MANY, TLWE>(sh.ct[s], sh.tw, g, t, mu, u_a + (size_t)gct * kN, u_b + gct,
+                                                    (size_t)gct, live, l.tv, l.mo, acc_sample<TLWE>(in, idx));
 }
 
 template <int WAVES, bool RREG, bool LUT = false, bool MANY = false>
@@ -748,12 +757,12 @@ hipError_t launch_blind_rotate_v6(const DeviceKey &key, int B, int halves, const
         with_mode(mode, [&](auto m) {
             with_flag(paired ? ps : rreg, [&](auto f) {
                 constexpr bool F = decltype(f)::value, LUT = mode_lut(decltype(m)::value),
-                               MANY = mode_many(decltype(m)::value);
+                               MANY = mode_many(decltype(m)::value), TLWE = mode_tlwe(decltype(m)::value);
                 if (paired)
-                    hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, F, LUT, MANY>), dim3((unsigned)wgs),
+                    hipLaunchKernelGGL((k_blind_rotate_v6p<kV6Waves, F, LUT, MANY, TLWE>), dim3((unsigned)wgs),
                                        dim3(2 * kV6Threads), 0, s, g, B, (int)total, (int)base, in[0], in1, mu, u_a, u_b);
                 else
-                    hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, F, LUT, MANY>), dim3((unsigned)wgs),
+                    hipLaunchKernelGGL((k_blind_rotate_v6<kV6Waves, F, LUT, MANY, TLWE>), dim3((unsigned)wgs),
                                        dim3(kV6Threads), 0, s, g, B, (int)base, in[0], in1, mu, u_a, u_b);
             });
         });
@@ -765,7 +774,7 @@ hipError_t launch_blind_rotate_v6_rows(const DeviceKey &key, int B, int nrows, c
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
                                        BrMode mode, const Guard *guard) {
     if (B <= 0 || nrows <= 0) return hipSuccess;
-    if (!key.bk_fft) return hipErrorInvalidValue;
+    if (!key.bk_fft || mode == BrMode::Tlwe) return hipErrorInvalidValue;   // no rows form of the tlwe mode
     const long total = (long)B * nrows, chunk = v6_chunk(key);
     for (long base = 0; base < total; base += chunk) {
         const long n = total - base < chunk ? total - base : chunk;

@@ -82,6 +82,20 @@ __device__ __forceinline__ LutArgs lut_args(const CircRow *rec, const CircRow &r
     return l;
 }
 
+// The accumulator sample of ciphertext idx of an encrypted-accumulator launch (engine.h BrInput.acc):
+// the index comes from device memory unchecked by the host, so it is clamped into [0, n_acc) before
+// it forms an address.  Compile-time null for every other instantiation.
+template <bool TLWE>
+__device__ __forceinline__ const int32_t *acc_sample(const BrInput in, int idx) {
+    if constexpr (TLWE) {
+        int t = in.acc_index ? in.acc_index[idx] : in.n_acc == 1 ? 0 : idx;
+        t = t < in.n_acc ? t : in.n_acc - 1;
+        t = t > 0 ? t : 0;
+        return in.acc + (size_t)t * 2 * kN;
+    }
+    return nullptr;
+}
+
 // gate prologue + modulus switching (lwe-bootstrapping-functions-fft.cu:1851-1858) by the THREADS
 // threads of one ciphertext: bara[0 .. kn) and barb, rotation amounts < 2N (MANY: multiples of 2^th)
 template <bool MANY, int THREADS, typename T>
@@ -109,6 +123,7 @@ namespace {   // host helpers of the two launcher files, not library symbols
 template <class F>
 void with_mode(BrMode mode, F &&f) {
     switch (mode) {
+    case BrMode::Tlwe: return f(std::integral_constant<BrMode, BrMode::Tlwe>{});
     case BrMode::Many: return f(std::integral_constant<BrMode, BrMode::Many>{});
     case BrMode::Lut: return f(std::integral_constant<BrMode, BrMode::Lut>{});
     default: return f(std::integral_constant<BrMode, BrMode::Const>{});
@@ -118,11 +133,12 @@ template <class F>
 void with_flag(bool flag, F &&f) {
     return flag ? f(std::true_type{}) : f(std::false_type{});
 }
-constexpr bool mode_lut(BrMode m) { return m != BrMode::Const; }
+constexpr bool mode_lut(BrMode m) { return m == BrMode::Lut || m == BrMode::Many; }
 constexpr bool mode_many(BrMode m) { return m == BrMode::Many; }
+constexpr bool mode_tlwe(BrMode m) { return m == BrMode::Tlwe; }
 
 // The trace name of a launch (engine.h trace_kernel), from the same choices: the kernel's name,
-// then in parentheses the mode (lut / lut-many; nothing for the constant form) and the form's
+// then in parentheses the mode (lut / lut-many / tlwe; nothing for the constant form) and the form's
 // non-null parts, joined by '+'; the bare name when there is nothing to say.
 struct KernelLabel {
     char s[96];
@@ -134,7 +150,7 @@ struct KernelLabel {
             n += (size_t)snprintf(s + n, sizeof s - n, "%s%s", sep, part);
             sep = "+";
         };
-        add(mode == BrMode::Many ? "lut-many" : mode == BrMode::Lut ? "lut" : nullptr);
+        add(mode == BrMode::Many ? "lut-many" : mode == BrMode::Lut ? "lut" : mode == BrMode::Tlwe ? "tlwe" : nullptr);
         for (const char *part : form) add(part);
         if (*sep == '+' && n < sizeof s) snprintf(s + n, sizeof s - n, ")");
     }

@@ -573,6 +573,14 @@ int tfhe_amd_internal_frame(TfheAmdContext *c, void *stream, int u_slots, int (*
     return rc;
 }
 
+// batch_dev for entry points that live outside this file and bring their own BrInput (engine.h)
+int tfhe_amd_internal_br_batch(TfheAmdContext *c, void *stream, int B, const BrInput *in, int32_t *u_a, int32_t *u_b,
+                               int32_t *res_a, int32_t *res_b) {
+    if (!c || !in || B <= 0 || !c->key.has_bk || (res_a && !c->key.ksk)) return TFHE_AMD_E_ARG;
+    if (res_a) return batch_dev(c, stream, B, B, 1, in, 0, nullptr, nullptr, B, 0, res_a, res_b);
+    return batch_dev(c, stream, B, B, 1, in, 0, u_a, u_b);
+}
+
 extern "C" int tfhe_amd_gate_batch_dev(TfheAmdContext *c, int gate, int B, int32_t *res_a, int32_t *res_b,
                                        const int32_t *ca_a, const int32_t *ca_b, const int32_t *cb_a,
                                        const int32_t *cb_b, const int32_t *cc_a, const int32_t *cc_b,

@@ -53,6 +53,15 @@ struct BrInput {
     // it (sc != 0 needs tv and z_a, z_b); the constant kernels keep two inputs.
     const int32_t *z_a = nullptr, *z_b = nullptr;
     int32_t sc = 0;
+    // bootstrap from an encrypted accumulator: with acc set the accumulator starts
+    // from X^{2N - barb} (acc_a, acc_b), a TLWE sample out of acc [n_acc][2][kN] (a, then b) on the
+    // device, instead of a trivial sample.  Ciphertext g takes sample acc_index[g], clamped by the
+    // kernel into [0, n_acc) before any address is formed; a null index means sample 0 when
+    // n_acc == 1 and sample g otherwise.  One half, two input terms, no tables, one output; the
+    // guard launch recomputes a flagged ciphertext from the same sample, so u must not alias acc.
+    const int32_t *acc = nullptr;
+    const int32_t *acc_index = nullptr;
+    int32_t n_acc = 0;
 };
 
 // One bootstrapped row of a circuit level (circuit.cpp): the blind rotation input is
@@ -139,10 +148,17 @@ uint32_t guard_threshold_hi();
 // test vectors with several extracted outputs (many-LUT; implies Lut).  A rows launch is told its
 // mode (the row records are in device memory): Lut if some row of the level carries a test vector
 // (CircRow.lut), Many if some row is a many-LUT row (CircRow.many).
-enum class BrMode { Const, Lut, Many };
+// Tlwe: the accumulator starts from an encrypted TLWE sample (BrInput.acc); gate launches only.
+enum class BrMode { Const, Lut, Many, Tlwe };
 // The mode of a launch over in[0 .. halves), or hipErrorInvalidValue for an inconsistent one.
 inline hipError_t br_mode(const BrInput *in, int halves, BrMode *mode) {
     const BrInput &in1 = halves > 1 ? in[1] : in[0];
+    // encrypted accumulator: one half, at least one sample, and none of the table forms' fields
+    if (in[0].acc || in1.acc) {
+        if (halves != 1 || in[0].n_acc <= 0 || in[0].tv || in[0].n_out != 0 || in[0].sc) return hipErrorInvalidValue;
+        *mode = BrMode::Tlwe;
+        return hipSuccess;
+    }
     // programmable bootstrap: every half carries its tables (n_lut >= 1), or none does
     const bool lut = in[0].tv != nullptr;
     if (lut != (in1.tv != nullptr) || (lut && (in[0].n_lut <= 0 || in1.n_lut <= 0))) return hipErrorInvalidValue;
@@ -224,6 +240,15 @@ hipError_t launch_tgsw_v1_to_v2(const uint32_t *d_v1, uint32_t *d_v2, int count,
 int pack_split(int T, int cus);
 hipError_t launch_pack(const DeviceKey &key, const uint32_t *pack_key, int T, int P, const int32_t *in_a,
                        const int32_t *in_b, const int32_t *pos, uint32_t *dig, int G, int32_t *out, hipStream_t s);
+// The pack of p-way selection: as launch_pack with function-major inputs, in_a
+// [P][T_total][kn] and in_b [P][T_total] offset to the first of the T outputs of this launch, and
+// input p at coefficient p * pos_step.  The digit kernel's trace name is "k_pack_digits(function-major)".
+hipError_t launch_pack_fm(const DeviceKey &key, const uint32_t *pack_key, int T, int P, int T_total,
+                          const int32_t *in_a, const int32_t *in_b, int pos_step, uint32_t *dig, int G, int32_t *out,
+                          hipStream_t s);
+// Box fill (tlwe_box_fill.hip): out = in * (1 + X + ... + X^(2^log_w - 1)), negacyclic, exact mod 2^32,
+// over the 2 T polynomials of T TLWE samples [T][2][kN]; out may be in
+hipError_t launch_tlwe_box_fill(int T, int log_w, const int32_t *in, int32_t *out, hipStream_t s);
 // circuit level (v4 kernel): B instances x nrows rows, wires [W][B] ciphertexts, u slots r B + k
 hipError_t launch_blind_rotate_v4_rows(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
@@ -290,3 +315,9 @@ struct ContextFrame {
 struct TfheAmdContext;
 int tfhe_amd_internal_frame(TfheAmdContext *c, void *stream, int u_slots,
                             int (*fn)(const tfhe_amd::ContextFrame &, void *), void *arg);
+// One blind-rotation batch of B ciphertexts from `in` (one half) in the frame of the device entry
+// points of engine.cpp: selected kernel, guard, profile scopes, scratch fence.  res_a set: followed by
+// the key switch into (res_a, res_b) through the context's scratch; else the extracted samples go to
+// (u_a, u_b).  The caller has checked its arrays; TFHE_AMD_E_ARG for a context without the keys needed.
+int tfhe_amd_internal_br_batch(TfheAmdContext *c, void *stream, int B, const tfhe_amd::BrInput *in, int32_t *u_a,
+                               int32_t *u_b, int32_t *res_a, int32_t *res_b);

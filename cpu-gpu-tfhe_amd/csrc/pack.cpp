@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "pack_key.h"
 #include "../../include/tfhe_amd.h"
 
 using namespace tfhe_amd;
@@ -20,19 +21,6 @@ using namespace tfhe_amd;
             return TFHE_AMD_E_HIP;                                                \
         }                                                                         \
     } while (0)
-
-// The 3 000 key rows on `device` as 750 groups in the exact kernels' key layout (DeviceKey.bk_v2),
-// 64 KB each, and the digit scratch of the pack calls: 2 MB per output of the largest batch so far,
-// shared by every pack on the key, so its reuse is ordered across streams like a set's tree scratch.
-struct TfheAmdPackKey {
-    int device = -1;
-    int cus = 0;   // compute units of the device: the split of the key rows is chosen from it
-    uint32_t *v2 = nullptr;
-    std::mutex mu;
-    uint32_t *dig = nullptr;
-    size_t dig_outputs = 0;
-    StreamFence fence;
-};
 
 namespace {
 
@@ -186,6 +174,7 @@ extern "C" int tfhe_amd_pack_key_destroy(TfheAmdPackKey *key) {
         (void)hipDeviceSynchronize();   // launches on caller streams may still read the key
         key->fence.release();
         if (key->dig) (void)hipFree(key->dig);
+        if (key->acc) (void)hipFree(key->acc);
         if (key->v2) (void)hipFree(key->v2);
     }
     delete key;

@@ -8,7 +8,9 @@
 // Two kernels per batch of outputs:
 //   k_pack_digits  transposes the masks into the key object's scratch dig [T][500][kN]: word
 //                  (i, pos[p]) holds the six 4-bit digits of a_p[i], unoccupied positions the digits
-//                  of 0; it also writes (0, sum_p b_p X^pos[p]) into the output;
+//                  of 0; it also writes (0, sum_p b_p X^pos[p]) into the output
+//                  (k_pack_digits_fm: the same pass over function-major inputs [P][T][500] at the
+//                  positions p * pos_step, for the p-way selection of DESIGN.md §3.8);
 //   k_pack_v4      one workgroup per (output, slice of the 3 000 key rows), two waves, one per
 //                  prime: digits -> ntt_fwd<4> -> Montgomery MAC against key group g, summed in the
 //                  NTT domain; every kPackChunkUnits units one inverse transform, CRT lift and
@@ -50,19 +52,22 @@ struct PackArgs {
 // before any address is formed from it (the same for every workgroup of the launch).  Duplicate
 // positions race on one LDS word or one output word: the output is unspecified, nothing is out of
 // bounds.
-__global__ __launch_bounds__(256) void k_pack_digits(int P, const int32_t *__restrict__ in_a,
-                                                     const int32_t *__restrict__ in_b, const int32_t *__restrict__ pos,
-                                                     uint32_t *__restrict__ dig, int32_t *__restrict__ out) {
+// The body takes output t's inputs as a (mask of input 0, columns from i0 on) and b (body of input 0)
+// with the strides a_p, b_p from one input to the next, and the position of input p as pos[p], or
+// p * pos_step for a null pos: the two kernels below differ only in these.
+__device__ __forceinline__ void pack_digits_body(int P, const int32_t *__restrict__ a, size_t a_p,
+                                                 const int32_t *__restrict__ b, size_t b_p,
+                                                 const int32_t *__restrict__ pos, int pos_step,
+                                                 uint32_t *__restrict__ dig, int32_t *__restrict__ out) {
     __shared__ uint32_t tile[kDigitTile][kN];
     uint32_t *flat = &tile[0][0];
     const int tid = threadIdx.x, t = blockIdx.y, i0 = blockIdx.x * kDigitTile;
     for (int k = tid; k < kDigitTile * kN; k += 256) flat[k] = kPackOffset >> 8;
     __syncthreads();
-    const int32_t *a = in_a + (size_t)t * P * kn + i0;
     for (int k = tid; k < P * kDigitTile; k += 256) {
         const int p = k / kDigitTile, c = k - p * kDigitTile;
-        const int j = pos ? pos[p] : p;
-        if ((unsigned)j < (unsigned)kN) tile[c][j] = ((uint32_t)a[(size_t)p * kn + c] + kPackOffset) >> 8;
+        const int j = pos ? pos[p] : p * pos_step;
+        if ((unsigned)j < (unsigned)kN) tile[c][j] = ((uint32_t)a[(size_t)p * a_p + c] + kPackOffset) >> 8;
     }
     __syncthreads();
     uint32_t *d = dig + ((size_t)t * kn + i0) * kN;
@@ -72,8 +77,8 @@ __global__ __launch_bounds__(256) void k_pack_digits(int P, const int32_t *__res
     for (int k = tid; k < kN; k += 256) tile[0][k] = 0;
     __syncthreads();
     for (int p = tid; p < P; p += 256) {
-        const int j = pos ? pos[p] : p;
-        if ((unsigned)j < (unsigned)kN) tile[0][j] = (uint32_t)in_b[(size_t)t * P + p];
+        const int j = pos ? pos[p] : p * pos_step;
+        if ((unsigned)j < (unsigned)kN) tile[0][j] = (uint32_t)b[(size_t)p * b_p];
     }
     __syncthreads();
     int32_t *o = out + (size_t)t * 2 * kN;
@@ -81,6 +86,21 @@ __global__ __launch_bounds__(256) void k_pack_digits(int P, const int32_t *__res
         o[k] = 0;
         o[kN + k] = (int32_t)tile[0][k];
     }
+}
+__global__ __launch_bounds__(256) void k_pack_digits(int P, const int32_t *__restrict__ in_a,
+                                                     const int32_t *__restrict__ in_b, const int32_t *__restrict__ pos,
+                                                     uint32_t *__restrict__ dig, int32_t *__restrict__ out) {
+    const int t = blockIdx.y, i0 = blockIdx.x * kDigitTile;
+    pack_digits_body(P, in_a + (size_t)t * P * kn + i0, kn, in_b + (size_t)t * P, 1, pos, 1, dig, out);
+}
+// function-major inputs: in_a [P][T_total][kn], in_b [P][T_total], input p of
+// output t at coefficient p * pos_step (P * pos_step <= kN is the launcher's check)
+__global__ __launch_bounds__(256) void k_pack_digits_fm(int P, int T_total, const int32_t *__restrict__ in_a,
+                                                        const int32_t *__restrict__ in_b, int pos_step,
+                                                        uint32_t *__restrict__ dig, int32_t *__restrict__ out) {
+    const int t = blockIdx.y, i0 = blockIdx.x * kDigitTile;
+    pack_digits_body(P, in_a + (size_t)t * kn + i0, (size_t)T_total * kn, in_b + t, (size_t)T_total, nullptr, pos_step, dig,
+                     out);
 }
 
 // centred CRT lift of lazy residues x0 in [0, 2 q0), x1 in [0, 2 q1), reduced mod 2^32: the lift of
@@ -242,12 +262,15 @@ int pack_split(int T, int cus) {
     return G < 2 ? 1 : G > kPackUnits / 2 ? kPackUnits / 2 : G;
 }
 
-hipError_t launch_pack(const DeviceKey &key, const uint32_t *pack_key, int T, int P, const int32_t *in_a,
-                       const int32_t *in_b, const int32_t *pos, uint32_t *dig, int G, int32_t *out, hipStream_t s) {
+// fm_total > 0: the function-major form of launch_pack_fm with T_total = fm_total and pos_step
+static hipError_t pack_launches(const DeviceKey &key, const uint32_t *pack_key, int T, int P, const int32_t *in_a,
+                                const int32_t *in_b, const int32_t *pos, int fm_total, int pos_step, uint32_t *dig, int G,
+                                int32_t *out, hipStream_t s) {
     if (T <= 0) return hipSuccess;
     if (!pack_key || !key.tw2 || !key.tw4 || T > kPackMaxBatch || P < 1 || P > kN || !in_a || !in_b || !dig || !out ||
         G < 1 || G > kPackUnits)
         return hipErrorInvalidValue;
+    if (fm_total > 0 && (T > fm_total || pos_step < 1 || (long)(P - 1) * pos_step >= kN)) return hipErrorInvalidValue;
     PackArgs g;
     g.key = pack_key;
     g.tu_f = key.tw2;
@@ -259,8 +282,14 @@ hipError_t launch_pack(const DeviceKey &key, const uint32_t *pack_key, int T, in
     g.qinv_neg1 = key.qinv_neg[1];
     g.crt_h = key.crt_h;
     g.crt_hp = key.crt_hp;
-    trace_kernel("k_pack_digits");
-    hipLaunchKernelGGL(k_pack_digits, dim3(kn / kDigitTile, T), dim3(256), 0, s, P, in_a, in_b, pos, dig, out);
+    if (fm_total > 0) {
+        trace_kernel("k_pack_digits(function-major)");
+        hipLaunchKernelGGL(k_pack_digits_fm, dim3(kn / kDigitTile, T), dim3(256), 0, s, P, fm_total, in_a, in_b, pos_step,
+                           dig, out);
+    } else {
+        trace_kernel("k_pack_digits");
+        hipLaunchKernelGGL(k_pack_digits, dim3(kn / kDigitTile, T), dim3(256), 0, s, P, in_a, in_b, pos, dig, out);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int upw = (kPackUnits + G - 1) / G;        // units per workgroup
@@ -268,6 +297,18 @@ hipError_t launch_pack(const DeviceKey &key, const uint32_t *pack_key, int T, in
     trace_kernel(grid > 1 ? "k_pack_v4(split)" : "k_pack_v4");
     hipLaunchKernelGGL(k_pack_v4, dim3(grid, T), dim3(kPackThreads), 0, s, g, upw, grid > 1 ? 1 : 0, dig, out);
     return hipGetLastError();
+}
+
+hipError_t launch_pack(const DeviceKey &key, const uint32_t *pack_key, int T, int P, const int32_t *in_a,
+                       const int32_t *in_b, const int32_t *pos, uint32_t *dig, int G, int32_t *out, hipStream_t s) {
+    return pack_launches(key, pack_key, T, P, in_a, in_b, pos, 0, 1, dig, G, out, s);
+}
+
+hipError_t launch_pack_fm(const DeviceKey &key, const uint32_t *pack_key, int T, int P, int T_total,
+                          const int32_t *in_a, const int32_t *in_b, int pos_step, uint32_t *dig, int G, int32_t *out,
+                          hipStream_t s) {
+    if (T_total <= 0) return hipErrorInvalidValue;
+    return pack_launches(key, pack_key, T, P, in_a, in_b, nullptr, T_total, pos_step, dig, G, out, s);
 }
 
 }  // namespace tfhe_amd

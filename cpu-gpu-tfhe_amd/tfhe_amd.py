@@ -156,6 +156,19 @@ def _load():
     L.tfhe_amd_pack_key_destroy.argtypes = [_VP]
     L.tfhe_amd_pack_dev.argtypes = [_VP, _VP, ctypes.c_int, ctypes.c_int] + [_VP] * 4 + [_VP]
     L.tfhe_amd_pack_host.argtypes = [_VP, _VP, ctypes.c_int, ctypes.c_int] + [_I32P] * 4
+    # bootstrap from encrypted accumulators (tfhe_amd_tlwe_box_fill_*, tfhe_amd_bootstrap_acc_*, tfhe_amd_select_*)
+    L.tfhe_amd_tlwe_box_fill_dev.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP]
+    L.tfhe_amd_tlwe_box_fill_host.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _I32P, _I32P]
+    for f in ("tfhe_amd_bootstrap_acc_woks_batch_dev", "tfhe_amd_bootstrap_acc_batch_dev"):
+        getattr(L, f).argtypes = ([_VP, ctypes.c_int, ctypes.c_int, _VP, _VP, ctypes.c_int32, ctypes.c_int32, _VP, _VP,
+                                   ctypes.c_int32] + [_VP] * 4 + [_VP])
+    for f in ("tfhe_amd_bootstrap_acc_woks_batch_host", "tfhe_amd_bootstrap_acc_batch_host"):
+        getattr(L, f).argtypes = ([_VP, ctypes.c_int, ctypes.c_int, _I32P, _I32P, ctypes.c_int32, ctypes.c_int32, _I32P,
+                                   _I32P, ctypes.c_int32] + [_I32P] * 4)
+    L.tfhe_amd_select_batch_dev.argtypes = ([_VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, ctypes.c_int32,
+                                             ctypes.c_int32] + [_VP] * 4 + [_VP])
+    L.tfhe_amd_select_batch_host.argtypes = ([_VP, _VP, ctypes.c_int, ctypes.c_int, _I32P, _I32P, ctypes.c_int32,
+                                              ctypes.c_int32] + [_I32P] * 4)
     return L
 
 
@@ -951,6 +964,110 @@ class Context:
             self._dev_check(t, shape, name)
         _check(lib.tfhe_amd_pack_dev(self.h, pkey.h, T_, P, in_a.data_ptr(), in_b.data_ptr(),
                                      None if pos is None else pos.data_ptr(), out.data_ptr(), stream), "pack_dev")
+
+    # ---- bootstrap from encrypted accumulators: acc = TLWE samples [n_acc][2][1024]
+    # (or one [2][1024]); acc_index [B] picks each ciphertext's accumulator (None: accumulator 0 when
+    # n_acc == 1, accumulator i when n_acc == B); the selector is (0, c) + sa X + sb Y
+    def box_fill_host(self, tlwe, log_w):
+        """tfhe_amd_tlwe_box_fill_host: tlwe [T][2][1024] (or one [2][1024]) -> tlwe (1 + X + ... +
+        X^(2^log_w - 1)), same shape"""
+        tlwe = i32(tlwe)
+        if tlwe.ndim < 2 or tlwe.shape[-2:] != (2, N):
+            raise TfheAmdError(f"need TLWE samples [T][2][1024], got {tlwe.shape}")
+        out = np.zeros(tlwe.shape, np.int32)
+        _check(lib.tfhe_amd_tlwe_box_fill_host(self.h, tlwe.size // (2 * N), int(log_w), _p(tlwe), _p(out)),
+               "tlwe_box_fill_host")
+        return out
+
+    def box_fill_dev(self, tlwe, out, log_w, stream=None):
+        """tfhe_amd_tlwe_box_fill_dev on torch tensors [T][2][1024]; out may be tlwe; asynchronous"""
+        if tlwe is None or tlwe.dim() != 3:
+            raise TfheAmdError("need a GPU tensor [T][2][1024]")
+        T_ = tlwe.shape[0]
+        for name, t in (("tlwe", tlwe), ("out", out)):
+            self._dev_check(t, (T_, 2, N), name)
+        _check(lib.tfhe_amd_tlwe_box_fill_dev(self.h, T_, int(log_w), tlwe.data_ptr(), out.data_ptr(), stream),
+               "tlwe_box_fill_dev")
+
+    def _acc_host(self, ks, acc, x_a, x_b, acc_index, c, sa, sb, y_a, y_b):
+        acc = i32(acc).reshape(-1, 2, N)
+        x_a = i32(x_a); B = x_a.shape[0]
+        idx = None if acc_index is None else i32(acc_index)
+        if idx is not None and idx.shape != (B,):
+            raise TfheAmdError(f"acc_index: need one accumulator index per ciphertext ({B}), got {idx.shape}")
+        if int(sb) != 0 and (y_a is None or y_b is None):
+            raise TfheAmdError("sb != 0 needs y_a, y_b")
+        r_a = np.zeros((B, n_lwe if ks else N), np.int32); r_b = np.zeros(B, np.int32)
+        name = "bootstrap_acc" + ("" if ks else "_woks") + "_batch_host"
+        _check(getattr(lib, "tfhe_amd_" + name)(
+            self.h, B, acc.shape[0], _p(acc), _p(idx), int(c), int(sa), _p(x_a), _p(i32(x_b)), int(sb),
+            _p(None if y_a is None else i32(y_a)), _p(None if y_b is None else i32(y_b)), _p(r_a), _p(r_b)), name)
+        return r_a, r_b
+
+    def acc_woks_host(self, acc, x_a, x_b, acc_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None):
+        """tfhe_amd_bootstrap_acc_woks_batch_host -> the extracted samples (u_a [B][1024], u_b [B])"""
+        return self._acc_host(False, acc, x_a, x_b, acc_index, c, sa, sb, y_a, y_b)
+
+    def acc_bootstrap_host(self, acc, x_a, x_b, acc_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None):
+        """tfhe_amd_bootstrap_acc_batch_host -> the key-switched results (r_a [B][500], r_b [B])"""
+        return self._acc_host(True, acc, x_a, x_b, acc_index, c, sa, sb, y_a, y_b)
+
+    def _acc_dev(self, ks, acc, out_a, out_b, x_a, x_b, acc_index, c, sa, sb, y_a, y_b, stream):
+        B = x_a.shape[0]
+        if acc is None or acc.dim() != 3 or acc.shape[0] < 1:
+            raise TfheAmdError("acc: need a GPU tensor [n_acc][2][1024]")
+        n_acc = acc.shape[0]
+        named = [("acc", acc, (n_acc, 2, N)), ("out_a", out_a, (B, n_lwe if ks else N)), ("out_b", out_b, (B,)),
+                 ("x_a", x_a, (B, n_lwe)), ("x_b", x_b, (B,))]
+        if acc_index is not None:
+            named.append(("acc_index", acc_index, (B,)))
+        if int(sb) != 0:
+            named += [("y_a", y_a, (B, n_lwe)), ("y_b", y_b, (B,))]
+        for name, t, shape in named:
+            self._dev_check(t, shape, name)
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        name = "bootstrap_acc" + ("" if ks else "_woks") + "_batch_dev"
+        _check(getattr(lib, "tfhe_amd_" + name)(
+            self.h, B, n_acc, ptr(acc), ptr(acc_index), int(c), int(sa), ptr(x_a), ptr(x_b), int(sb),
+            ptr(y_a) if int(sb) else None, ptr(y_b) if int(sb) else None, ptr(out_a), ptr(out_b), stream), name)
+
+    def acc_woks_dev(self, acc, u_a, u_b, x_a, x_b, acc_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None, stream=None):
+        """tfhe_amd_bootstrap_acc_woks_batch_dev on torch tensors; an acc_index entry outside [0, n_acc)
+        is clamped by the kernel; u must not overlap acc"""
+        self._acc_dev(False, acc, u_a, u_b, x_a, x_b, acc_index, c, sa, sb, y_a, y_b, stream)
+
+    def acc_bootstrap_dev(self, acc, res_a, res_b, x_a, x_b, acc_index=None, c=0, sa=1, sb=0, y_a=None, y_b=None,
+                          stream=None):
+        """tfhe_amd_bootstrap_acc_batch_dev on torch tensors; res may alias x"""
+        self._acc_dev(True, acc, res_a, res_b, x_a, x_b, acc_index, c, sa, sb, y_a, y_b, stream)
+
+    def select_host(self, pkey, cand_a, cand_b, y_a, y_b, c=0, sa=1):
+        """tfhe_amd_select_batch_host: candidates cand_a [p][B][500], cand_b [p][B] (function-major),
+        selectors (0, c) + sa Y -> (r_a [B][500], r_b [B]), query q the candidate in the box of its
+        selector's phase"""
+        cand_a = i32(cand_a); cand_b = i32(cand_b)
+        if cand_a.ndim != 3 or cand_a.shape[2] != n_lwe or cand_b.shape != cand_a.shape[:2]:
+            raise TfheAmdError(f"need cand_a [p][B][500] and cand_b [p][B], got {cand_a.shape}, {cand_b.shape}")
+        p, B = cand_b.shape
+        y_a = i32(y_a); y_b = i32(y_b)
+        if y_a.shape != (B, n_lwe) or y_b.shape != (B,):
+            raise TfheAmdError(f"need y_a [{B}][500] and y_b [{B}], got {y_a.shape}, {y_b.shape}")
+        r_a = np.zeros((B, n_lwe), np.int32); r_b = np.zeros(B, np.int32)
+        _check(lib.tfhe_amd_select_batch_host(self.h, pkey.h, B, p, _p(cand_a), _p(cand_b), int(c), int(sa), _p(y_a),
+                                              _p(y_b), _p(r_a), _p(r_b)), "select_batch_host")
+        return r_a, r_b
+
+    def select_dev(self, pkey, cand_a, cand_b, y_a, y_b, res_a, res_b, c=0, sa=1, stream=None):
+        """tfhe_amd_select_batch_dev on torch tensors (shapes as select_host); asynchronous"""
+        if cand_b is None or cand_b.dim() != 2:
+            raise TfheAmdError("need GPU tensors cand_a [p][B][500] and cand_b [p][B]")
+        p, B = cand_b.shape
+        for name, t, shape in (("cand_a", cand_a, (p, B, n_lwe)), ("cand_b", cand_b, (p, B)), ("y_a", y_a, (B, n_lwe)),
+                               ("y_b", y_b, (B,)), ("res_a", res_a, (B, n_lwe)), ("res_b", res_b, (B,))):
+            self._dev_check(t, shape, name)
+        _check(lib.tfhe_amd_select_batch_dev(self.h, pkey.h, B, p, cand_a.data_ptr(), cand_b.data_ptr(), int(c),
+                                             int(sa), y_a.data_ptr(), y_b.data_ptr(), res_a.data_ptr(),
+                                             res_b.data_ptr(), stream), "select_batch_dev")
 
     def blind_rotate_dev(self, acc, bara, iters, stream=None):
         B = acc.shape[0]

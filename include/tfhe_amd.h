@@ -424,6 +424,82 @@ int tfhe_amd_pack_dev(TfheAmdContext *ctx, TfheAmdPackKey *key, int T, int P, co
 int tfhe_amd_pack_host(TfheAmdContext *ctx, TfheAmdPackKey *key, int T, int P, const int32_t *in_a,
                        const int32_t *in_b, const int32_t *pos, int32_t *out);
 
+/* ---- Bootstrap from encrypted accumulators: a computed digit selects among
+ * computed values.  Every other bootstrap starts its blind rotation from a trivial sample
+ * (0, X^-bar(b) tv) with a plaintext tv; these start from X^-bar(b) (A, B), a TLWE ciphertext the
+ * server made itself (tfhe_amd_pack_* and the box fill below), so the selector's digit picks a
+ * coefficient of a table of computed values: the second level of tree-based programmable
+ * bootstrapping.  The 500 CMux steps, the exactness guard (a flagged ciphertext is recomputed from the
+ * same accumulator), tfhe_amd_select_kernel and the extraction at coefficient 0 are those of every
+ * bootstrap; the output's noise is the accumulator's plus a blind rotation's.
+ *
+ * tfhe_amd_tlwe_box_fill_*: out = in (1 + X + ... + X^(w-1)), w = 2^log_w, on both polynomials of T
+ * TLWE samples [T][2][1024], negacyclic and exact mod 2^32: out[j] = sum_{k<w} +-in[(j-k) mod 1024],
+ * minus where j - k < 0.  A sample packed with value m at coefficient m w (and nothing between the
+ * occupied positions) then carries value m over the whole box [m w, (m+1) w) of the LUT convention,
+ * which is what a rotation by a noisy selector needs.  out may be in; log_w = 0 is a copy.
+ * TFHE_AMD_E_ARG for T < 0, log_w outside [0, 10] and null arrays with T > 0.  Trace name
+ * "k_tlwe_box_fill". */
+int tfhe_amd_tlwe_box_fill_dev(TfheAmdContext *ctx, int T, int log_w, const int32_t *in, int32_t *out,
+                               void *stream);
+int tfhe_amd_tlwe_box_fill_host(TfheAmdContext *ctx, int T, int log_w, const int32_t *in, int32_t *out);
+
+/* B bootstraps from the accumulators acc [n_acc][2][1024] (a, then b).  The selector is
+ * (0, c) + sa*X + sb*Y as in the LUT forms (Y ignored, may be NULL, when sb == 0); ciphertext i starts
+ * from accumulator acc_index[i]; acc_index = NULL means accumulator 0 when n_acc == 1 and accumulator
+ * i when n_acc == B, and is TFHE_AMD_E_ARG for any other n_acc.  The woks forms return
+ * SampleExtract_0 of the rotated accumulator, u_a [B][1024], u_b [B]; the others key switch it into
+ * res_a [B][500], res_b [B].  No output may alias acc (the guard's recomputation reads it again);
+ * res may alias X.  The _dev forms take device arrays and are asynchronous on `stream`; the kernel
+ * clamps each acc_index entry into [0, n_acc) before it forms an address.  The _host forms stage
+ * through temporary device buffers, are synchronous and return TFHE_AMD_E_ARG for an acc_index entry
+ * outside [0, n_acc), writing nothing.  TFHE_AMD_E_ARG also for n_acc <= 0, B < 0, null arrays and,
+ * in the key-switched forms, a context without key-switching key.  tfhe_amd_last_kernels names the
+ * variants with "tlwe" where the LUT forms say "lut", e.g. "k_blind_rotate_v6(tlwe+reg-rotation)",
+ * "k_blind_rotate_v4(tlwe+guard)". */
+int tfhe_amd_bootstrap_acc_woks_batch_dev(TfheAmdContext *ctx, int B, int n_acc, const int32_t *acc,
+                                          const int32_t *acc_index, int32_t c, int32_t sa,
+                                          const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                          const int32_t *y_a, const int32_t *y_b,
+                                          int32_t *u_a, int32_t *u_b, void *stream);
+int tfhe_amd_bootstrap_acc_batch_dev(TfheAmdContext *ctx, int B, int n_acc, const int32_t *acc,
+                                     const int32_t *acc_index, int32_t c, int32_t sa,
+                                     const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                     const int32_t *y_a, const int32_t *y_b,
+                                     int32_t *res_a, int32_t *res_b, void *stream);
+int tfhe_amd_bootstrap_acc_woks_batch_host(TfheAmdContext *ctx, int B, int n_acc, const int32_t *acc,
+                                           const int32_t *acc_index, int32_t c, int32_t sa,
+                                           const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                           const int32_t *y_a, const int32_t *y_b,
+                                           int32_t *u_a, int32_t *u_b);
+int tfhe_amd_bootstrap_acc_batch_host(TfheAmdContext *ctx, int B, int n_acc, const int32_t *acc,
+                                      const int32_t *acc_index, int32_t c, int32_t sa,
+                                      const int32_t *x_a, const int32_t *x_b, int32_t sb,
+                                      const int32_t *y_a, const int32_t *y_b,
+                                      int32_t *res_a, int32_t *res_b);
+
+/* The composed p-way selector, p a power of two in [2, 1024].  cand_a [p][B][500], cand_b [p][B] are
+ * the candidates, function-major: exactly what tfhe_amd_bootstrap_lut_many_batch_* or p LUT batches
+ * write.  Query q's selector is (0, c) + sa*Y_q.  Four steps: the pack of B outputs of p inputs with
+ * candidate m at coefficient m (1024 / p), into the pack key's accumulator scratch (8 KB per query,
+ * beside its digit scratch, grown and fenced across streams the same way); the box fill with
+ * log_w = 10 - log2 p; the rotation of accumulator q by selector q; the key switch.  res_q has the
+ * phase of cand[m_q][q] plus noise, m_q the box of the selector's phase among the p boxes of [0, 1/2);
+ * a selector phase in [1/2, 1) gives the negated candidate.  A gate bit (+-1/8) selects with p = 2,
+ * c = 1/4, sa = 1.  With bootstrapped candidates and a bootstrapped selector p <= 4 decodes with
+ * margin.  res may alias Y or the candidates.  TFHE_AMD_E_ARG for a p that is no
+ * such power of two, B < 0, null arrays, a null key or context, a key on another device and a context
+ * without bootstrapping or key-switching key; B = 0 returns TFHE_AMD_OK.  tfhe_amd_last_kernels lists
+ * "k_pack_digits(function-major)", the pack kernel, "k_tlwe_box_fill", the tlwe rotation and the key
+ * switch in order. */
+int tfhe_amd_select_batch_dev(TfheAmdContext *ctx, TfheAmdPackKey *pack_key, int B, int p,
+                              const int32_t *cand_a, const int32_t *cand_b, int32_t c, int32_t sa,
+                              const int32_t *y_a, const int32_t *y_b, int32_t *res_a, int32_t *res_b,
+                              void *stream);
+int tfhe_amd_select_batch_host(TfheAmdContext *ctx, TfheAmdPackKey *pack_key, int B, int p,
+                               const int32_t *cand_a, const int32_t *cand_b, int32_t c, int32_t sa,
+                               const int32_t *y_a, const int32_t *y_b, int32_t *res_a, int32_t *res_b);
+
 /* Timing of the engine's own kernels (HIP events on the stream they run on):
  * enable=1 starts accumulating; read returns the summed ms and launch counts of the
  * blind-rotation kernel and the key-switch kernel since enabling. */
