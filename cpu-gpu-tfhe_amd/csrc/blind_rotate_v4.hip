@@ -249,13 +249,17 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4(V4Args g, 
 
 // circuit level: flat slot r B + k (row r, instance k < B), grid-stride as the gate kernel;
 // wires are [W][B] ciphertexts, the extracted sample of (r, k) goes to u slot r B + k
-template <int MINW, bool LUT = false, bool MANY = false>
+// TLWE (a level's select rows): slot r B + k starts from the TLWE sample of the same
+// index in acc, formed here from the slot alone
+template <int MINW, bool LUT = false, bool MANY = false, bool TLWE = false>
 __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4_rows(V4Args g, int B, long total,
                                                                      const CircRow *__restrict__ rows,
                                                                      const int32_t *__restrict__ wa,
                                                                      const int32_t *__restrict__ wb, int32_t mu,
                                                                      int32_t *__restrict__ u_a,
-                                                                     int32_t *__restrict__ u_b, V4Guard gd) {
+                                                                     int32_t *__restrict__ u_b, V4Guard gd,
+                                                                     const int32_t *__restrict__ acc) {
+    static_assert(!TLWE || (!LUT && !MANY), "the tlwe form excludes the table forms");
     __shared__ V4Shared sh;
     bool used = false;
     for (long slot = blockIdx.x; slot < total; slot += gridDim.x) {
@@ -267,7 +271,8 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4_rows(V4Arg
         RowTerms t;
         row_terms(t, row, wa, wb, B, k);
         const LutArgs l = lut_args<LUT, MANY>(rows + r, row, B, k, u_a, u_b);
-        br_v4_body<LUT, MANY>(sh, g, t, mu, u_a + (size_t)slot * kN, u_b + slot, l.tv, l.mo);
+        br_v4_body<LUT, MANY, TLWE>(sh, g, t, mu, u_a + (size_t)slot * kN, u_b + slot, l.tv, l.mo,
+                                    TLWE ? acc + (size_t)slot * 2 * kN : nullptr);
     }
 }
 
@@ -479,7 +484,7 @@ hipError_t launch_blind_rotate_v4_rows(const DeviceKey &key, int B, int nrows, c
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
                                        BrMode mode, const Guard *guard) {
     if (B <= 0 || nrows <= 0) return hipSuccess;
-    if (!key.bk_v2 || mode == BrMode::Tlwe) return hipErrorInvalidValue;   // no rows form of the tlwe mode
+    if (!key.bk_v2 || mode == BrMode::Tlwe) return hipErrorInvalidValue;   // the tlwe rows form has its own launcher
     const V4Guard gd = v4_guard(guard);
     const long total = (long)B * nrows;
     const long grid = gd.flags && total > kGuardGrid ? kGuardGrid : total < 0x7fffffffL ? total : 0x7fffffffL;
@@ -489,8 +494,24 @@ hipError_t launch_blind_rotate_v4_rows(const DeviceKey &key, int B, int nrows, c
             hipLaunchKernelGGL((k_blind_rotate_v4_rows<decltype(f)::value ? 1 : 2, mode_lut(decltype(m)::value),
                                                        mode_many(decltype(m)::value)>),
                                dim3((unsigned)grid), dim3(kV4Threads), 0, s, v4_args(key), B, total, rows, wa, wb, mu, u_a,
-                               u_b, gd);
+                               u_b, gd, (const int32_t *)nullptr);
         });
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_blind_rotate_v4_rows_tlwe(const DeviceKey &key, int B, int nrows, const CircRow *rows,
+                                            const int32_t *wa, const int32_t *wb, const int32_t *acc, int32_t *u_a,
+                                            int32_t *u_b, hipStream_t s, const Guard *guard) {
+    if (B <= 0 || nrows <= 0) return hipSuccess;
+    if (!key.bk_v2 || !acc || !rows) return hipErrorInvalidValue;
+    const V4Guard gd = v4_guard(guard);
+    const long total = (long)B * nrows;
+    const long grid = gd.flags && total > kGuardGrid ? kGuardGrid : total < 0x7fffffffL ? total : 0x7fffffffL;
+    trace_kernel(KernelLabel("k_blind_rotate_v4_rows", BrMode::Tlwe, {gd.flags ? "guard" : nullptr}).s);
+    with_flag(gd.flags != nullptr, [&](auto f) {
+        hipLaunchKernelGGL((k_blind_rotate_v4_rows<decltype(f)::value ? 1 : 2, false, false, true>), dim3((unsigned)grid),
+                           dim3(kV4Threads), 0, s, v4_args(key), B, total, rows, wa, wb, (int32_t)0, u_a, u_b, gd, acc);
     });
     return hipGetLastError();
 }

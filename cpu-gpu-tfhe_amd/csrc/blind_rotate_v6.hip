@@ -534,13 +534,17 @@ __global__ __launch_bounds__(2 * kV6Threads, WAVES) void k_blind_rotate_v6p(V6Ar
                                                     (size_t)gct, live, l.tv, l.mo, acc_sample<TLWE>(in, idx));
 }
 
-template <int WAVES, bool RREG, bool LUT = false, bool MANY = false>
+// TLWE (a level's select rows): slot r B + k starts from the TLWE sample r B + k of
+// acc; the index is formed here from r, B, k alone, nothing is read from memory for it
+template <int WAVES, bool RREG, bool LUT = false, bool MANY = false, bool TLWE = false>
 __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6_rows(V6Args g, int B, long base,
                                                                      const CircRow *__restrict__ rows,
                                                                      const int32_t *__restrict__ wa,
                                                                      const int32_t *__restrict__ wb, int32_t mu,
                                                                      int32_t *__restrict__ u_a,
-                                                                     int32_t *__restrict__ u_b) {
+                                                                     int32_t *__restrict__ u_b,
+                                                                     const int32_t *__restrict__ acc) {
+    static_assert(!TLWE || (!LUT && !MANY), "the tlwe form excludes the table forms");
     __shared__ V6Shared sh;
     const long flat = base + blockIdx.x;          // row-major (row, instance)
     const int r = (int)(flat / B), k = (int)(flat - (long)r * B);
@@ -549,8 +553,8 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6_rows(V6Ar
     row_terms(t, row, wa, wb, B, k);
     const size_t slot = (size_t)r * B + k;
     const LutArgs l = lut_args<LUT, MANY>(rows + r, row, B, k, u_a, u_b);
-    br_v6_body<WAVES, RREG, 1, false, LUT, MANY>(sh.ct[0], sh.tw, g, t, mu, u_a + slot * kN, u_b + slot, slot, true, l.tv,
-                                                 l.mo);
+    br_v6_body<WAVES, RREG, 1, false, LUT, MANY, TLWE>(sh.ct[0], sh.tw, g, t, mu, u_a + slot * kN, u_b + slot, slot, true,
+                                                       l.tv, l.mo, TLWE ? acc + slot * 2 * kN : nullptr);
 }
 
 template <bool RREG>
@@ -774,7 +778,7 @@ hipError_t launch_blind_rotate_v6_rows(const DeviceKey &key, int B, int nrows, c
                                        const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
                                        BrMode mode, const Guard *guard) {
     if (B <= 0 || nrows <= 0) return hipSuccess;
-    if (!key.bk_fft || mode == BrMode::Tlwe) return hipErrorInvalidValue;   // no rows form of the tlwe mode
+    if (!key.bk_fft || mode == BrMode::Tlwe) return hipErrorInvalidValue;   // the tlwe rows form has its own launcher
     const long total = (long)B * nrows, chunk = v6_chunk(key);
     for (long base = 0; base < total; base += chunk) {
         const long n = total - base < chunk ? total - base : chunk;
@@ -786,8 +790,28 @@ hipError_t launch_blind_rotate_v6_rows(const DeviceKey &key, int B, int nrows, c
                 hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, decltype(f)::value, mode_lut(decltype(m)::value),
                                                            mode_many(decltype(m)::value)>),
                                    dim3((unsigned)n), dim3(kV6Threads), 0, s, v6_args(key, n, guard), B, base, rows, wa, wb,
-                                   mu, u_a, u_b);
+                                   mu, u_a, u_b, (const int32_t *)nullptr);
             });
+        });
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_blind_rotate_v6_rows_tlwe(const DeviceKey &key, int B, int nrows, const CircRow *rows,
+                                            const int32_t *wa, const int32_t *wb, const int32_t *acc, int32_t *u_a,
+                                            int32_t *u_b, hipStream_t s, const Guard *guard) {
+    if (B <= 0 || nrows <= 0) return hipSuccess;
+    if (!key.bk_fft || !acc || !rows) return hipErrorInvalidValue;
+    const long total = (long)B * nrows, chunk = v6_chunk(key);
+    for (long base = 0; base < total; base += chunk) {
+        const long n = total - base < chunk ? total - base : chunk;
+        if (n > 0x7fffffffL) return hipErrorInvalidValue;
+        const bool rreg = v6_rreg(key, n);
+        trace_kernel(KernelLabel("k_blind_rotate_v6_rows", BrMode::Tlwe, {rreg ? "reg-rotation" : "lds-rotation"}).s);
+        with_flag(rreg, [&](auto f) {
+            hipLaunchKernelGGL((k_blind_rotate_v6_rows<kV6Waves, decltype(f)::value, false, false, true>),
+                               dim3((unsigned)n), dim3(kV6Threads), 0, s, v6_args(key, n, guard), B, base, rows, wa, wb,
+                               (int32_t)0, u_a, u_b, acc);
         });
     }
     return hipGetLastError();

@@ -26,6 +26,7 @@
 #include "engine.h"
 #include "../../include/tfhe_amd.h"
 #include "api_internal.h"
+#include "circuit_internal.h"
 
 using namespace tfhe_amd;
 
@@ -44,12 +45,15 @@ struct Node {
     // many-LUT node (gate kManyGate): n_out consecutive wires, one Node each, that share one
     // bootstrapped row; index = the wire's position in the node (the extraction index)
     int log_nu = 0, n_out = 1, index = 0;
+    int sel = -1;        // select node (gate kSelGate): its candidates' entry in TfheAmdCircuit::selnodes
 };
 constexpr int kLutGate = -2;   // gate code of a LUT node (tfhe_amd_circuit_node)
 constexpr int kManyGate = -3;  // gate code of every wire of a many-LUT node
 constexpr int kAffineGate = -4;  // gate code of an affine node (0, c0) + s[0] W[in[0]] (kind 2)
 constexpr int32_t kH0 = 1 << 28;   // half-torus bit 0: 1/16; bit 1 is 3 kH0
+constexpr int kSelGate = -5;     // gate code of a select node: the selector is (0, c0) + s[0] W[in[0]]
 constexpr int kExtraRow = 1 << 30;   // compile: a u row behind the level's rows, until their number is known
+constexpr int kSelRow = 1 << 29;     // compile: the u row of a select row, until the level's other u rows are known
 
 struct Affine {          // W = (0, c) + s W[base]; base = -1: the trivial sample (0, c)
     int32_t c, s;
@@ -87,11 +91,25 @@ struct TfheAmdCircuit {
     bool compiled = false;
     // lut: some row carries a test vector; many: some row is a many-LUT row; urows: u rows the
     // level writes (nrows + the further outputs of its many-LUT rows)
-    struct Level { int row0, nrows, ks0, nks, lin0, nlin; bool lut; bool many = false; int urows = 0; };
+    // select rows: nsel of them from sel0 on in srows / sels, grouped by p; their u rows
+    // are usel .. usel + nsel - 1, behind the level's other u rows (urows counts them too)
+    struct Level {
+        int row0, nrows, ks0, nks, lin0, nlin;
+        bool lut;
+        bool many = false;
+        int urows = 0;
+        int sel0 = 0, nsel = 0, usel = 0;
+    };
     std::vector<Level> levels;         // levels[0]: affine nodes over inputs only
     std::vector<CircRow> rows;
     std::vector<CircKs> ks;
     std::vector<CircLin> lin;
+    // select nodes: the candidate wires of each (Node.sel), and the compiled rows: selector and
+    // candidate record of select row i are srows[i], sels[i]
+    struct SelNode { int p; int cand[16]; };
+    std::vector<SelNode> selnodes;
+    std::vector<CircRow> srows;
+    std::vector<CircSel> sels;
     // programmable-bootstrap test vectors [n][kN]; uploaded behind the level tables, where the LUT
     // rows find them by a self-relative offset (engine.h CircRow.lut)
     std::vector<int32_t> luts;
@@ -189,8 +207,13 @@ int compile(TfheAmdCircuit *C) {
     std::vector<std::vector<CircKs>> kss;
     std::vector<std::vector<CircLin>> lins;
     std::vector<int> extras;   // per level: u rows behind the level's rows (many-LUT outputs f >= 1)
+    std::vector<std::vector<CircRow>> srows;   // per level: the select rows' selectors and records
+    std::vector<std::vector<CircSel>> sels;
     auto ensure = [&](int L) {
-        if ((int)rows.size() <= L) { rows.resize(L + 1); kss.resize(L + 1); lins.resize(L + 1); extras.resize(L + 1, 0); }
+        if ((int)rows.size() <= L) {
+            rows.resize(L + 1); kss.resize(L + 1); lins.resize(L + 1); extras.resize(L + 1, 0);
+            srows.resize(L + 1); sels.resize(L + 1);
+        }
     };
     ensure(0);
     C->n_boot = 0;
@@ -221,6 +244,31 @@ int compile(TfheAmdCircuit *C) {
         if (nd.gate == kManyGate && nd.index > 0) {   // a further output of the row its first wire made
             level[w] = level[w - nd.index];
             aff[w] = Affine{0, 1, w};
+            continue;
+        }
+        if (nd.gate == kSelGate) {
+            // a select row: candidates are read as materialised wires, the selector folds like a row input
+            const TfheAmdCircuit::SelNode &sn = C->selnodes[nd.sel];
+            const Affine A = aff[nd.in[0]];
+            int L = A.base >= 0 ? level[A.base] : 0;
+            CircSel rec;
+            rec.p = sn.p;
+            for (int m = 0; m < 16; ++m) {
+                rec.w[m] = m < sn.p ? sn.cand[m] : -1;
+                if (m >= sn.p) continue;
+                if (sn.cand[m] < 0 || sn.cand[m] >= w) return TFHE_AMD_E_ARG;
+                L = std::max(L, level[sn.cand[m]]);
+            }
+            L += 1;
+            ensure(L);
+            level[w] = L;
+            aff[w] = Affine{0, 1, w};
+            CircRow r;
+            build_row(nd.c0, nd.s, &A, 1, &r);
+            srows[L].push_back(r);
+            sels[L].push_back(rec);
+            kss[L].push_back(CircKs{kSelRow + (int)srows[L].size() - 1, -1, 0, w});
+            C->n_boot += 1;
             continue;
         }
         // bootstrapped
@@ -266,20 +314,35 @@ int compile(TfheAmdCircuit *C) {
             C->n_boot += 1;
         }
     }
-    C->levels.clear(); C->rows.clear(); C->ks.clear(); C->lin.clear();
+    C->levels.clear(); C->rows.clear(); C->ks.clear(); C->lin.clear(); C->srows.clear(); C->sels.clear();
     C->max_rows = 0;
     for (size_t L = 0; L < rows.size(); ++L) {
         TfheAmdCircuit::Level lv{(int)C->rows.size(), (int)rows[L].size(), (int)C->ks.size(), (int)kss[L].size(),
                                  (int)C->lin.size(), (int)lins[L].size(), false};
-        lv.urows = lv.nrows + extras[L];
+        lv.sel0 = (int)C->srows.size();
+        lv.nsel = (int)srows[L].size();
+        lv.usel = lv.nrows + extras[L];
+        lv.urows = lv.usel + lv.nsel;
         if (lv.urows > 65535) return TFHE_AMD_E_ARG;
+        // select rows grouped by p (the box fill's width is uniform within a launch): a stable sort,
+        // place[i] = where the level's i-th select row went
+        std::vector<int> order(lv.nsel), place(lv.nsel);
+        for (int i = 0; i < lv.nsel; ++i) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return sels[L][a].p < sels[L][b].p; });
+        for (int i = 0; i < lv.nsel; ++i) {
+            place[order[i]] = i;
+            C->srows.push_back(srows[L][order[i]]);
+            C->sels.push_back(sels[L][order[i]]);
+        }
         for (CircRow &r : rows[L]) {
             lv.lut = lv.lut || r.lut != 0;
             lv.many = lv.many || r.many != 0;
             if (r.many) r.urow = lv.nrows + (r.urow - kExtraRow);
         }
-        for (CircKs &k : kss[L])
+        for (CircKs &k : kss[L]) {
             if (k.r1 >= kExtraRow) k.r1 = lv.nrows + (k.r1 - kExtraRow);
+            else if (k.r1 >= kSelRow) k.r1 = lv.usel + place[k.r1 - kSelRow];
+        }
         C->rows.insert(C->rows.end(), rows[L].begin(), rows[L].end());
         C->ks.insert(C->ks.end(), kss[L].begin(), kss[L].end());
         C->lin.insert(C->lin.end(), lins[L].begin(), lins[L].end());
@@ -287,7 +350,7 @@ int compile(TfheAmdCircuit *C) {
         C->max_rows = std::max(C->max_rows, lv.urows);
     }
     // a LUT row's test vector: words from the row's own record to its table in the uploaded block
-    // [rows | ks | lin | tables] (tfhe_amd_circuit_run_dev_impl)
+    // [rows | ks | lin | tables | select rows | select records] (tfhe_amd_circuit_run_dev_hook)
     const size_t head = (sizeof(CircRow) * C->rows.size() + sizeof(CircKs) * C->ks.size() +
                          sizeof(CircLin) * C->lin.size()) / 4;
     if (head + C->luts.size() > 0x7fffffffu) return TFHE_AMD_E_ARG;
@@ -496,6 +559,55 @@ extern "C" int tfhe_amd_circuit_full_add(TfheAmdCircuit *c, int a, int b, int ci
     return TFHE_AMD_OK;
 }
 
+// Select node: the box of the selector's phase among the p boxes of [0, 1/2) picks
+// the candidate wire; one bootstrapped row of its own kind, levelled behind the selector's base and
+// every candidate
+extern "C" int tfhe_amd_circuit_select(TfheAmdCircuit *c, int p, const int *cand, int32_t c0, int32_t s, int sel) {
+    if (!c || !cand || (p != 2 && p != 4 && p != 8 && p != 16) || !wire_ok(c, sel)) return TFHE_AMD_E_ARG;
+    TfheAmdCircuit::SelNode sn;
+    sn.p = p;
+    for (int m = 0; m < 16; ++m) {
+        sn.cand[m] = m < p ? cand[m] : -1;
+        if (m < p && !wire_ok(c, cand[m])) return TFHE_AMD_E_ARG;
+    }
+    Node n{1, kSelGate, c0, {s, 0, 0}, {sel, -1, -1}};
+    n.sel = (int)c->selnodes.size();
+    const int w = add_node(c, n);
+    if (w >= 0) c->selnodes.push_back(sn);
+    return w;
+}
+
+extern "C" int tfhe_amd_circuit_select_node(const TfheAmdCircuit *c, int w, int *p, int *cand, int32_t *c0) {
+    if (!c || w < 0 || w >= (int)c->nodes.size() || c->nodes[w].gate != kSelGate) return TFHE_AMD_E_ARG;
+    const TfheAmdCircuit::SelNode &sn = c->selnodes[c->nodes[w].sel];
+    if (p) *p = sn.p;
+    if (cand)
+        for (int m = 0; m < 16; ++m) cand[m] = sn.cand[m];
+    if (c0) *c0 = c->nodes[w].c0;
+    return TFHE_AMD_OK;
+}
+
+// number of select nodes (the run forms without a pack key refuse a circuit that has one)
+extern "C" int tfhe_amd_circuit_select_count(const TfheAmdCircuit *c) {
+    return c ? (int)c->selnodes.size() : TFHE_AMD_E_ARG;
+}
+
+// A function of two 2-bit digits (p = 4 boxes of [0, 1/2)) in two rotations: one many-LUT row on x
+// whose output j is m -> values[4 j + m], then a select node over the four outputs driven by y.
+// Returns the wire of values[4 y + x].
+extern "C" int tfhe_amd_circuit_lut2(TfheAmdCircuit *c, const int32_t *values, int x, int y) {
+    if (!c || !values || !wire_ok(c, x) || !wire_ok(c, y)) return TFHE_AMD_E_ARG;
+    // tfhe_amd_lut_fill_many(tv, 4, 2, 4, values): coefficient j holds function j mod 4 of box floor(4 j / N)
+    int32_t tv[kN];
+    for (int j = 0; j < kN; ++j) tv[j] = values[4 * (j & 3) + ((j * 4) >> kLogN)];
+    const int table = tfhe_amd_circuit_lut_table(c, tv);
+    if (table < 0) return table;
+    const int w = tfhe_amd_circuit_lut_many(c, table, 2, 4, 0, 1, x, 0, -1, 0, -1);
+    if (w < 0) return w;
+    const int cand[4] = {w, w + 1, w + 2, w + 3};
+    return tfhe_amd_circuit_select(c, 4, cand, 0, 1, y);
+}
+
 extern "C" int tfhe_amd_circuit_lut_node(const TfheAmdCircuit *c, int w, int *table, int32_t *c0) {
     if (!c || w < 0 || w >= (int)c->nodes.size() || c->nodes[w].gate != kLutGate) return TFHE_AMD_E_ARG;
     if (table) *table = c->nodes[w].table;
@@ -510,6 +622,7 @@ extern "C" int tfhe_amd_circuit_node(const TfheAmdCircuit *c, int w, int *kind, 
     if (kind) *kind = n.kind;
     if (gate) *gate = n.gate;
     // a LUT / many-LUT node: the table id (tfhe_amd_circuit_lut_node, tfhe_amd_circuit_lut_many_node)
+    // (a select node: the selector's constant; its candidates with tfhe_amd_circuit_select_node)
     if (c0) *c0 = n.gate == kLutGate || n.gate == kManyGate ? n.table : n.c0;
     for (int t = 0; t < 3; ++t) {
         if (s) s[t] = n.s[t];
@@ -543,7 +656,7 @@ extern "C" int tfhe_amd_circuit_level_sizes(TfheAmdCircuit *c, int *rows_per_lev
         if (rc != TFHE_AMD_OK) return rc;
     }
     const int nl = (int)c->levels.size();
-    for (int L = 0; L < nl && L < cap; ++L) rows_per_level[L] = c->levels[L].nrows;
+    for (int L = 0; L < nl && L < cap; ++L) rows_per_level[L] = c->levels[L].nrows + c->levels[L].nsel;
     return nl;
 }
 
@@ -552,6 +665,13 @@ extern "C" int tfhe_amd_circuit_level_sizes(TfheAmdCircuit *c, int *rows_per_lev
 // compiled schedule); runs on distinct contexts may overlap.
 int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int device, hipStream_t s,
                                   TfheAmdCircuit *c, int B, int32_t *wa, int32_t *wb, uint32_t *guard_stats) {
+    return tfhe_amd_circuit_run_dev_hook(ctx_uid, key, device, s, c, B, wa, wb, guard_stats, nullptr);
+}
+
+// hook: the select part of a level (circuit_internal.h); null: a circuit with a select node is refused
+int tfhe_amd_circuit_run_dev_hook(uint64_t ctx_uid, const DeviceKey &key, int device, hipStream_t s,
+                                  TfheAmdCircuit *c, int B, int32_t *wa, int32_t *wb, uint32_t *guard_stats,
+                                  const CircSelectHook *hook) {
     CircuitDevState *st;
     {
         std::lock_guard<std::mutex> lk(c->mu);
@@ -559,6 +679,7 @@ int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int de
             const int rc = compile(c);
             if (rc != TFHE_AMD_OK) return rc;   // (compile drops the states of the earlier schedule)
         }
+        if (!c->sels.empty() && !(hook && hook->fn)) return TFHE_AMD_E_ARG;   // before anything is launched
         auto &slot = c->states[ctx_uid];
         if (!slot) slot.reset(new CircuitDevState());
         st = slot.get();
@@ -567,7 +688,8 @@ int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int de
         st->release();
         st->dev = device;
         const size_t bytes = sizeof(CircRow) * c->rows.size() + sizeof(CircKs) * c->ks.size() +
-                             sizeof(CircLin) * c->lin.size() + sizeof(int32_t) * c->luts.size() + 64;
+                             sizeof(CircLin) * c->lin.size() + sizeof(int32_t) * c->luts.size() +
+                             sizeof(CircRow) * c->srows.size() + sizeof(CircSel) * c->sels.size() + 64;
         if (hipMalloc(&st->d_tab, bytes) != hipSuccess) return TFHE_AMD_E_NOMEM;
         char *p = (char *)st->d_tab;
         if (!c->rows.empty() && hipMemcpy(p, c->rows.data(), sizeof(CircRow) * c->rows.size(),
@@ -580,6 +702,12 @@ int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int de
                                          hipMemcpyHostToDevice) != hipSuccess) return TFHE_AMD_E_HIP;
         p += sizeof(CircLin) * c->lin.size();   // the LUT rows' self-relative offsets (compile) point here
         if (!c->luts.empty() && hipMemcpy(p, c->luts.data(), sizeof(int32_t) * c->luts.size(),
+                                          hipMemcpyHostToDevice) != hipSuccess) return TFHE_AMD_E_HIP;
+        p += sizeof(int32_t) * c->luts.size();
+        if (!c->srows.empty() && hipMemcpy(p, c->srows.data(), sizeof(CircRow) * c->srows.size(),
+                                           hipMemcpyHostToDevice) != hipSuccess) return TFHE_AMD_E_HIP;
+        p += sizeof(CircRow) * c->srows.size();
+        if (!c->sels.empty() && hipMemcpy(p, c->sels.data(), sizeof(CircSel) * c->sels.size(),
                                           hipMemcpyHostToDevice) != hipSuccess) return TFHE_AMD_E_HIP;
     }
     const size_t need = (size_t)c->max_rows * B;
@@ -598,13 +726,25 @@ int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int de
     const CircRow *d_rows = (const CircRow *)st->d_tab;
     const CircKs *d_ks = (const CircKs *)(d_rows + c->rows.size());
     const CircLin *d_lin = (const CircLin *)(d_ks + c->ks.size());
+    const CircRow *d_srows = (const CircRow *)((const int32_t *)(d_lin + c->lin.size()) + c->luts.size());
+    const CircSel *d_sels = (const CircSel *)(d_srows + c->srows.size());
     for (const auto &lv : c->levels) {
-        if (lv.nrows) {
-            const Guard gd = guard_stats ? Guard{st->u_flags, guard_stats} : Guard{};
-            const BrMode mode = lv.many ? BrMode::Many : lv.lut ? BrMode::Lut : BrMode::Const;
-            const hipError_t e = launch_blind_rotate_rows(key, B, lv.nrows, d_rows + lv.row0, wa, wb, kE8, st->u_a,
-                                                          st->u_b, s, mode, &gd);
-            if (e != hipSuccess) return TFHE_AMD_E_HIP;
+        if (lv.nrows || lv.nsel) {
+            if (lv.nrows) {
+                const Guard gd = guard_stats ? Guard{st->u_flags, guard_stats} : Guard{};
+                const BrMode mode = lv.many ? BrMode::Many : lv.lut ? BrMode::Lut : BrMode::Const;
+                const hipError_t e = launch_blind_rotate_rows(key, B, lv.nrows, d_rows + lv.row0, wa, wb, kE8, st->u_a,
+                                                              st->u_b, s, mode, &gd);
+                if (e != hipSuccess) return TFHE_AMD_E_HIP;
+            }
+            if (lv.nsel) {   // the select rows: their own pack, box fill and rows launch, behind the level's others
+                const size_t off = (size_t)lv.usel * B;
+                const CircSelLevel sl{B, lv.nsel, (int)c->nodes.size(), c->sels.data() + lv.sel0, d_sels + lv.sel0,
+                                      d_srows + lv.sel0, wa, wb, st->u_a + off * kN, st->u_b + off,
+                                      guard_stats ? Guard{st->u_flags + 2 * off, guard_stats} : Guard{}};
+                const int rc = hook->fn(hook->arg, key, sl, s);
+                if (rc != TFHE_AMD_OK) return rc;
+            }
             if (launch_keyswitch_rows(key, B, lv.nks, d_ks + lv.ks0, st->u_a, st->u_b, wa, wb, s) != hipSuccess)
                 return TFHE_AMD_E_HIP;
         }

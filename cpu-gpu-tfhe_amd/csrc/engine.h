@@ -87,6 +87,15 @@ struct CircLin {
     int32_t c, s, in, out;
 };
 
+// One select row of a circuit level: the p candidate wires whose samples the digit
+// pass of the pack gathers, candidate m to coefficient m kN / p.  The row's selector is a CircRow of
+// its own.  The pack's digit kernel reads the record from device memory: p is clamped into [0, 16]
+// and a wire id outside [0, W) drops that candidate before an address is formed.
+struct CircSel {
+    int32_t p;
+    int32_t w[16];
+};
+
 // Makes `device` current for the scope of an entry point and gives the caller's current device
 // back at its end: a caller that works on another GPU (torch.cuda.set_device(1), then a
 // context on device 0) keeps its own current device, which HIP and torch allocate on.
@@ -148,7 +157,8 @@ uint32_t guard_threshold_hi();
 // test vectors with several extracted outputs (many-LUT; implies Lut).  A rows launch is told its
 // mode (the row records are in device memory): Lut if some row of the level carries a test vector
 // (CircRow.lut), Many if some row is a many-LUT row (CircRow.many).
-// Tlwe: the accumulator starts from an encrypted TLWE sample (BrInput.acc); gate launches only.
+// Tlwe: the accumulator starts from an encrypted TLWE sample (BrInput.acc); gate launches, and the
+// rows launches of a circuit level's select rows (launch_blind_rotate_*_rows_tlwe below).
 enum class BrMode { Const, Lut, Many, Tlwe };
 // The mode of a launch over in[0 .. halves), or hipErrorInvalidValue for an inconsistent one.
 inline hipError_t br_mode(const BrInput *in, int halves, BrMode *mode) {
@@ -246,6 +256,13 @@ hipError_t launch_pack(const DeviceKey &key, const uint32_t *pack_key, int T, in
 hipError_t launch_pack_fm(const DeviceKey &key, const uint32_t *pack_key, int T, int P, int T_total,
                           const int32_t *in_a, const int32_t *in_b, int pos_step, uint32_t *dig, int G, int32_t *out,
                           hipStream_t s);
+// The pack of a circuit level's select rows: as launch_pack for the outputs
+// t0 .. t0 + T - 1 of the level, output t = r B + k gathering the candidates of select row r (sel[r])
+// at instance k from the wire table wa [W][B][kn], wb [W][B]; out is offset to output t0.  The digit
+// kernel's trace name is "k_pack_digits_rows".
+hipError_t launch_pack_rows(const DeviceKey &key, const uint32_t *pack_key, int T, int t0, int B, int W,
+                            const CircSel *sel, const int32_t *wa, const int32_t *wb, uint32_t *dig, int G,
+                            int32_t *out, hipStream_t s);
 // Box fill (tlwe_box_fill.hip): out = in * (1 + X + ... + X^(2^log_w - 1)), negacyclic, exact mod 2^32,
 // over the 2 T polynomials of T TLWE samples [T][2][kN]; out may be in
 hipError_t launch_tlwe_box_fill(int T, int log_w, const int32_t *in, int32_t *out, hipStream_t s);
@@ -264,6 +281,16 @@ hipError_t launch_blind_rotate_v6_rows(const DeviceKey &key, int B, int nrows, c
                                        BrMode mode, const Guard *guard = nullptr);
 hipError_t launch_blind_rotate_v6_debug(const DeviceKey &key, int B, int iters, int32_t *acc,
                                         const int32_t *bara, hipStream_t s);
+// The rows launches of a level's select rows, mode Tlwe: row r at instance k starts
+// from sample r B + k of acc [nrows B][2][kN] (the index is formed on the device from r, B, k alone)
+// and rotates it by the row's selector; u slot and guard flags r B + k as in the other rows launches.
+// u must not alias acc (the guard launch recomputes a flagged slot from the same sample).
+hipError_t launch_blind_rotate_v6_rows_tlwe(const DeviceKey &key, int B, int nrows, const CircRow *rows,
+                                            const int32_t *wa, const int32_t *wb, const int32_t *acc, int32_t *u_a,
+                                            int32_t *u_b, hipStream_t s, const Guard *guard = nullptr);
+hipError_t launch_blind_rotate_v4_rows_tlwe(const DeviceKey &key, int B, int nrows, const CircRow *rows,
+                                            const int32_t *wa, const int32_t *wb, const int32_t *acc, int32_t *u_a,
+                                            int32_t *u_b, hipStream_t s, const Guard *guard = nullptr);
 // which blind-rotation kernel runs: 0 = default (v6), 4 = exact NTT (tfhe_amd_select_kernel)
 int br_version();
 // Launch trace: every launcher names the kernel (and variant) it enqueues; a batch entry point of
@@ -275,6 +302,11 @@ void trace_kernel(const char *name);
 hipError_t launch_blind_rotate_rows(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
                                     const int32_t *wb, int32_t mu, int32_t *u_a, int32_t *u_b, hipStream_t s,
                                     BrMode mode, const Guard *guard);
+// the same for a level's select rows (circuit_select.cpp): mode Tlwe from the samples
+// acc [nrows B][2][kN], v6 then the guard launch of v4, or v4 alone under tfhe_amd_select_kernel(4)
+hipError_t launch_blind_rotate_rows_tlwe(const DeviceKey &key, int B, int nrows, const CircRow *rows, const int32_t *wa,
+                                         const int32_t *wb, const int32_t *acc, int32_t *u_a, int32_t *u_b,
+                                         hipStream_t s, const Guard *guard);
 
 // which key-switch kernel the larger batches take: 5 (int8 MFMA), or 4 with TFHE_AMD_KS5=0
 int ks_version();

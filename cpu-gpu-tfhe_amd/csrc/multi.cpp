@@ -244,6 +244,7 @@ extern "C" int tfhe_amd_multi_circuit_run_dev(TfheAmdMulti *m, TfheAmdCircuit *c
     const int world = (int)m->ctx.size();
     for (int r = 0; r < world; ++r)
         if (counts[r] < 0 || (counts[r] > 0 && (!wires_a[r] || !wires_b[r]))) return TFHE_AMD_E_ARG;
+    if (tfhe_amd_circuit_select_count(circ) > 0) return TFHE_AMD_E_ARG;   // pack keys have no replicas
     int rc = tfhe_amd_circuit_info(circ, nullptr, nullptr, nullptr, nullptr);   // compile once, here
     if (rc != TFHE_AMD_OK) return rc;
     std::lock_guard<std::mutex> lk(m->mu);
@@ -291,6 +292,7 @@ extern "C" int tfhe_amd_multi_circuit_run_host(TfheAmdMulti *m, TfheAmdCircuit *
     if (!m || !circ || B < 0 || n_in < 0 || n_out < 0) return TFHE_AMD_E_ARG;
     if (B == 0) return TFHE_AMD_OK;
     if ((n_in && (!in_wires || !in_a || !in_b)) || (n_out && (!out_wires || !out_a || !out_b))) return TFHE_AMD_E_ARG;
+    if (tfhe_amd_circuit_select_count(circ) > 0) return TFHE_AMD_E_ARG;   // pack keys have no replicas
     int n_wires = 0;
     int rc = tfhe_amd_circuit_info(circ, &n_wires, nullptr, nullptr, nullptr);   // compile once, here
     if (rc != TFHE_AMD_OK) return rc;

@@ -10,7 +10,9 @@
 //                  (i, pos[p]) holds the six 4-bit digits of a_p[i], unoccupied positions the digits
 //                  of 0; it also writes (0, sum_p b_p X^pos[p]) into the output
 //                  (k_pack_digits_fm: the same pass over function-major inputs [P][T][500] at the
-//                  positions p * pos_step, for the p-way selection of DESIGN.md §3.8);
+//                  positions p * pos_step, for the p-way selection of DESIGN.md §3.8;
+//                  k_pack_digits_rows: the same pass gathering each output's inputs from a circuit's
+//                  wire table through a per-row record, for the select rows of DESIGN.md §3.9);
 //   k_pack_v4      one workgroup per (output, slice of the 3 000 key rows), two waves, one per
 //                  prime: digits -> ntt_fwd<4> -> Montgomery MAC against key group g, summed in the
 //                  NTT domain; every kPackChunkUnits units one inverse transform, CRT lift and
@@ -52,12 +54,21 @@ struct PackArgs {
 // before any address is formed from it (the same for every workgroup of the launch).  Duplicate
 // positions race on one LDS word or one output word: the output is unspecified, nothing is out of
 // bounds.
-// The body takes output t's inputs as a (mask of input 0, columns from i0 on) and b (body of input 0)
-// with the strides a_p, b_p from one input to the next, and the position of input p as pos[p], or
-// p * pos_step for a null pos: the two kernels below differ only in these.
-__device__ __forceinline__ void pack_digits_body(int P, const int32_t *__restrict__ a, size_t a_p,
-                                                 const int32_t *__restrict__ b, size_t b_p,
-                                                 const int32_t *__restrict__ pos, int pos_step,
+// The body takes output t's inputs through `in`: in.a(p) the mask of input p from column i0 on,
+// in.b(p) its body, in.live(p) false for an input that is dropped (constant true for the strided
+// forms); and the position of input p as pos[p], or p * pos_step for a null pos: the kernels below
+// differ only in these.
+struct PackStrided {   // input p at a fixed stride from input 0
+    const int32_t *__restrict__ a0;
+    size_t a_p;
+    const int32_t *__restrict__ b0;
+    size_t b_p;
+    __device__ __forceinline__ bool live(int) const { return true; }
+    __device__ __forceinline__ const int32_t *a(int p) const { return a0 + (size_t)p * a_p; }
+    __device__ __forceinline__ int32_t b(int p) const { return b0[(size_t)p * b_p]; }
+};
+template <class In>
+__device__ __forceinline__ void pack_digits_body(int P, const In in, const int32_t *__restrict__ pos, int pos_step,
                                                  uint32_t *__restrict__ dig, int32_t *__restrict__ out) {
     __shared__ uint32_t tile[kDigitTile][kN];
     uint32_t *flat = &tile[0][0];
@@ -67,7 +78,7 @@ __device__ __forceinline__ void pack_digits_body(int P, const int32_t *__restric
     for (int k = tid; k < P * kDigitTile; k += 256) {
         const int p = k / kDigitTile, c = k - p * kDigitTile;
         const int j = pos ? pos[p] : p * pos_step;
-        if ((unsigned)j < (unsigned)kN) tile[c][j] = ((uint32_t)a[(size_t)p * a_p + c] + kPackOffset) >> 8;
+        if (in.live(p) && (unsigned)j < (unsigned)kN) tile[c][j] = ((uint32_t)in.a(p)[c] + kPackOffset) >> 8;
     }
     __syncthreads();
     uint32_t *d = dig + ((size_t)t * kn + i0) * kN;
@@ -78,7 +89,7 @@ __device__ __forceinline__ void pack_digits_body(int P, const int32_t *__restric
     __syncthreads();
     for (int p = tid; p < P; p += 256) {
         const int j = pos ? pos[p] : p * pos_step;
-        if ((unsigned)j < (unsigned)kN) tile[0][j] = (uint32_t)b[(size_t)p * b_p];
+        if (in.live(p) && (unsigned)j < (unsigned)kN) tile[0][j] = (uint32_t)in.b(p);
     }
     __syncthreads();
     int32_t *o = out + (size_t)t * 2 * kN;
@@ -91,7 +102,7 @@ __global__ __launch_bounds__(256) void k_pack_digits(int P, const int32_t *__res
                                                      const int32_t *__restrict__ in_b, const int32_t *__restrict__ pos,
                                                      uint32_t *__restrict__ dig, int32_t *__restrict__ out) {
     const int t = blockIdx.y, i0 = blockIdx.x * kDigitTile;
-    pack_digits_body(P, in_a + (size_t)t * P * kn + i0, kn, in_b + (size_t)t * P, 1, pos, 1, dig, out);
+    pack_digits_body(P, PackStrided{in_a + (size_t)t * P * kn + i0, kn, in_b + (size_t)t * P, 1}, pos, 1, dig, out);
 }
 // function-major inputs: in_a [P][T_total][kn], in_b [P][T_total], input p of
 // output t at coefficient p * pos_step (P * pos_step <= kN is the launcher's check)
@@ -99,8 +110,30 @@ __global__ __launch_bounds__(256) void k_pack_digits_fm(int P, int T_total, cons
                                                         const int32_t *__restrict__ in_b, int pos_step,
                                                         uint32_t *__restrict__ dig, int32_t *__restrict__ out) {
     const int t = blockIdx.y, i0 = blockIdx.x * kDigitTile;
-    pack_digits_body(P, in_a + (size_t)t * kn + i0, (size_t)T_total * kn, in_b + t, (size_t)T_total, nullptr, pos_step, dig,
-                     out);
+    pack_digits_body(P, PackStrided{in_a + (size_t)t * kn + i0, (size_t)T_total * kn, in_b + t, (size_t)T_total}, nullptr,
+                     pos_step, dig, out);
+}
+// a circuit level's select rows: output t0 + t = r B + k gathers the p = sel[r].p
+// candidates of select row r at instance k from the wire table wa [W][B][kn], wb [W][B], candidate m
+// at coefficient m (kN / p).  The record comes from device memory: p is clamped into [0, 16], and a
+// wire id outside [0, W) drops that candidate before an address is formed from it (the rule of pos).
+struct PackGather {
+    const CircSel *__restrict__ rec;
+    const int32_t *__restrict__ wa, *__restrict__ wb;
+    int W, B, k, i0;
+    __device__ __forceinline__ bool live(int p) const { return (unsigned)rec->w[p] < (unsigned)W; }
+    __device__ __forceinline__ const int32_t *a(int p) const { return wa + ((size_t)rec->w[p] * B + k) * kn + i0; }
+    __device__ __forceinline__ int32_t b(int p) const { return wb[(size_t)rec->w[p] * B + k]; }
+};
+__global__ __launch_bounds__(256) void k_pack_digits_rows(int B, int W, int t0, const CircSel *__restrict__ sel,
+                                                          const int32_t *__restrict__ wa,
+                                                          const int32_t *__restrict__ wb, uint32_t *__restrict__ dig,
+                                                          int32_t *__restrict__ out) {
+    const int t = t0 + blockIdx.y, i0 = blockIdx.x * kDigitTile;
+    const int r = t / B, k = t - r * B;
+    int P = sel[r].p;
+    P = P < 0 ? 0 : P > 16 ? 16 : P;
+    pack_digits_body(P, PackGather{sel + r, wa, wb, W, B, k, i0}, nullptr, P ? kN / P : 1, dig, out);
 }
 
 // centred CRT lift of lazy residues x0 in [0, 2 q0), x1 in [0, 2 q1), reduced mod 2^32: the lift of
@@ -262,10 +295,17 @@ int pack_split(int T, int cus) {
     return G < 2 ? 1 : G > kPackUnits / 2 ? kPackUnits / 2 : G;
 }
 
-// fm_total > 0: the function-major form of launch_pack_fm with T_total = fm_total and pos_step
+// the gather of launch_pack_rows
+struct PackRowsArgs {
+    int t0, B, W;
+    const CircSel *sel;
+};
+
+// fm_total > 0: the function-major form of launch_pack_fm with T_total = fm_total and pos_step;
+// rows: the gather form of launch_pack_rows (in_a, in_b the wire table)
 static hipError_t pack_launches(const DeviceKey &key, const uint32_t *pack_key, int T, int P, const int32_t *in_a,
                                 const int32_t *in_b, const int32_t *pos, int fm_total, int pos_step, uint32_t *dig, int G,
-                                int32_t *out, hipStream_t s) {
+                                int32_t *out, hipStream_t s, const PackRowsArgs *rows = nullptr) {
     if (T <= 0) return hipSuccess;
     if (!pack_key || !key.tw2 || !key.tw4 || T > kPackMaxBatch || P < 1 || P > kN || !in_a || !in_b || !dig || !out ||
         G < 1 || G > kPackUnits)
@@ -282,7 +322,12 @@ static hipError_t pack_launches(const DeviceKey &key, const uint32_t *pack_key, 
     g.qinv_neg1 = key.qinv_neg[1];
     g.crt_h = key.crt_h;
     g.crt_hp = key.crt_hp;
-    if (fm_total > 0) {
+    if (rows) {
+        if (!rows->sel || rows->B < 1 || rows->W < 1 || rows->t0 < 0) return hipErrorInvalidValue;
+        trace_kernel("k_pack_digits_rows");
+        hipLaunchKernelGGL(k_pack_digits_rows, dim3(kn / kDigitTile, T), dim3(256), 0, s, rows->B, rows->W, rows->t0,
+                           rows->sel, in_a, in_b, dig, out);
+    } else if (fm_total > 0) {
         trace_kernel("k_pack_digits(function-major)");
         hipLaunchKernelGGL(k_pack_digits_fm, dim3(kn / kDigitTile, T), dim3(256), 0, s, P, fm_total, in_a, in_b, pos_step,
                            dig, out);
@@ -309,6 +354,13 @@ hipError_t launch_pack_fm(const DeviceKey &key, const uint32_t *pack_key, int T,
                           hipStream_t s) {
     if (T_total <= 0) return hipErrorInvalidValue;
     return pack_launches(key, pack_key, T, P, in_a, in_b, nullptr, T_total, pos_step, dig, G, out, s);
+}
+
+hipError_t launch_pack_rows(const DeviceKey &key, const uint32_t *pack_key, int T, int t0, int B, int W,
+                            const CircSel *sel, const int32_t *wa, const int32_t *wb, uint32_t *dig, int G,
+                            int32_t *out, hipStream_t s) {
+    const PackRowsArgs rows{t0, B, W, sel};
+    return pack_launches(key, pack_key, T, 16, wa, wb, nullptr, 0, 1, dig, G, out, s, &rows);
 }
 
 }  // namespace tfhe_amd

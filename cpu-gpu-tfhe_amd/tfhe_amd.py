@@ -1283,6 +1283,12 @@ lib.tfhe_amd_circuit_level_sizes.argtypes = [_VP, _IP, ctypes.c_int]
 lib.tfhe_amd_circuit_node.argtypes = [_VP, ctypes.c_int, _IP, _IP, ctypes.POINTER(ctypes.c_int32),
                                       ctypes.POINTER(ctypes.c_int32), _IP]
 lib.tfhe_amd_circuit_run_dev.argtypes = [_VP, _VP, ctypes.c_int, _VP, _VP, _VP]
+SELECT_GATE = -5   # ... for a select node: the selector is (0, c0) + s[0] * W[in[0]]
+lib.tfhe_amd_circuit_select.argtypes = [_VP, ctypes.c_int, _IP, ctypes.c_int32, ctypes.c_int32, ctypes.c_int]
+lib.tfhe_amd_circuit_select_node.argtypes = [_VP, ctypes.c_int, _IP, _IP, ctypes.POINTER(ctypes.c_int32)]
+lib.tfhe_amd_circuit_select_count.argtypes = [_VP]
+lib.tfhe_amd_circuit_lut2.argtypes = [_VP, _I32P, ctypes.c_int, ctypes.c_int]
+lib.tfhe_amd_circuit_run_pk_dev.argtypes = [_VP, _VP, _VP, ctypes.c_int, _VP, _VP, _VP]
 lib.tfhe_amd_circuit_dot.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _IP, _IP, ctypes.c_int, _IP]
 lib.tfhe_amd_circuit_compare.argtypes = [_VP, ctypes.c_int, _IP, _IP, ctypes.c_int, ctypes.c_int]
 lib.tfhe_amd_circuit_minmax.argtypes = [_VP, ctypes.c_int, _IP, _IP, ctypes.c_int, ctypes.c_int, _IP]
@@ -1387,6 +1393,34 @@ class Circuit:
         _check(lib.tfhe_amd_circuit_lut_many_node(self.h, int(w), ctypes.byref(t), ctypes.byref(c0), ctypes.byref(th),
                                                   ctypes.byref(n), ctypes.byref(ix)), "circuit_lut_many_node")
         return t.value, c0.value, th.value, n.value, ix.value
+
+    def select(self, cand, sel, c0=0, s=1):
+        """tfhe_amd_circuit_select: the box of (0, c0) + s * sel among the p = len(cand) boxes of
+        [0, 1/2) picks one of the candidate wires (p in 2, 4, 8, 16); returns the new wire.  A circuit
+        with a select node runs with a pack key (run_dev(..., pack_key=))"""
+        cand = [int(x) for x in cand]
+        return self._w(lib.tfhe_amd_circuit_select(self.h, len(cand), _ids(cand) if cand else None, int(c0), int(s),
+                                                   int(sel)), "select")
+
+    def select_node(self, w):
+        """(p, candidate wires [p], c0) of the select node w (node(w) reports gate -5, the selector's
+        coefficient in s[0] and its wire in in[0])"""
+        p, c0 = ctypes.c_int(), ctypes.c_int32()
+        cand = (ctypes.c_int * 16)()
+        _check(lib.tfhe_amd_circuit_select_node(self.h, int(w), ctypes.byref(p), cand, ctypes.byref(c0)),
+               "circuit_select_node")
+        return p.value, list(cand[:p.value]), c0.value
+
+    def select_count(self):
+        return self._w(lib.tfhe_amd_circuit_select_count(self.h), "select_count")
+
+    def lut2(self, values, x, y):
+        """tfhe_amd_circuit_lut2: values [16] Torus32 (lut_encode(m, 4)); the wire of values[4 y + x] for
+        two p = 4 digit wires x, y: one many-LUT row on x, one select node driven by y"""
+        values = i32(values).reshape(-1)
+        if values.shape != (16,):
+            raise TfheAmdError(f"values: need 16 Torus32 words, got shape {values.shape}")
+        return self._w(lib.tfhe_amd_circuit_lut2(self.h, _p(values), int(x), int(y)), "lut2")
 
     # ---- one-rotation adder cells (include/tfhe_amd.h, DESIGN.md §3.4): G = gate bits (+-1/8),
     # H = half-torus bits (1/16, 3/16).  The library cannot check which one a wire carries.
@@ -1534,6 +1568,9 @@ class Circuit:
             if gate == LUT_MANY_GATE:
                 raise TfheAmdError(f"eval_plain evaluates bits; wire {w} belongs to a many-LUT node (multi-valued): "
                                    "evaluate it from its table (lut_many_node, lut_table_get)")
+            if gate == SELECT_GATE:
+                raise TfheAmdError(f"eval_plain evaluates bits; wire {w} is a select node (multi-valued): evaluate "
+                                   "it from its candidates (select_node)")
             if kind == 0:
                 val[w] = np.where(np.asarray(bits[w]) != 0, e8, -e8).astype(np.int64)
             elif kind == 2:
@@ -1556,7 +1593,7 @@ class Circuit:
                 val[w] = sign(x)
         return {w: (np.asarray(v) > 0).astype(np.int64) for w, v in val.items()}
 
-    def run(self, ctx, B, inputs, outputs, keyset, rng, stream=None):
+    def run(self, ctx, B, inputs, outputs, keyset, rng, stream=None, pack_key=None):
         """Encrypt `inputs` ({wire: bit array [B]}), run on the GPU, decrypt `outputs`
         (list of wires) -> {wire: bit array}.  Convenience for tests and the bench."""
         import torch
@@ -1567,12 +1604,17 @@ class Circuit:
             a, b = keyset.encrypt(np.asarray(bits), rng)
             wa[w] = torch.from_numpy(a).cuda()
             wb[w] = torch.from_numpy(b).cuda()
-        self.run_dev(ctx, B, wa, wb, stream)
+        self.run_dev(ctx, B, wa, wb, stream, pack_key=pack_key)
         torch.cuda.synchronize()
         ha, hb = wa.cpu().numpy(), wb.cpu().numpy()
         return {w: keyset.decrypt(ha[w], hb[w]) for w in outputs}
 
-    def run_dev(self, ctx, B, wa, wb, stream=None):
+    def run_dev(self, ctx, B, wa, wb, stream=None, pack_key=None):
+        """pack_key (PackKey): tfhe_amd_circuit_run_pk_dev, the run form a circuit with select nodes needs"""
+        if pack_key is not None:
+            _check(lib.tfhe_amd_circuit_run_pk_dev(ctx.h, pack_key.h, self.h, int(B), wa.data_ptr(), wb.data_ptr(),
+                                                   stream), "circuit_run_pk_dev")
+            return
         _check(lib.tfhe_amd_circuit_run_dev(ctx.h, self.h, int(B), wa.data_ptr(), wb.data_ptr(), stream),
                "circuit_run_dev")
 

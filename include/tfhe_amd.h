@@ -772,6 +772,40 @@ int tfhe_amd_circuit_info(TfheAmdCircuit *c, int *n_wires, int *n_gates, int *n_
 int tfhe_amd_circuit_level_sizes(TfheAmdCircuit *c, int *rows_per_level, int cap);
 int tfhe_amd_circuit_run_dev(TfheAmdContext *ctx, TfheAmdCircuit *c, int B, int32_t *wires_a, int32_t *wires_b,
                              void *stream);
+/* ---- Select nodes (the batch form: tfhe_amd_select_batch_*).  A computed digit picks
+ * among computed wires inside the DAG.  tfhe_amd_circuit_select adds one node on p in {2, 4, 8, 16}
+ * candidate wires cand[0 .. p) and the selector (0, c0) + s * W[sel]; it returns the output wire.
+ * Semantics are those of tfhe_amd_select_batch_*: the box of the selector's phase among the p boxes
+ * of [0, 1/2) picks the candidate, a phase in [1/2, 1) gives the NEGATED candidate; a gate bit
+ * selects with p = 2, c0 = 1/4, s = 1.  The candidates are read as written to their wires (any value,
+ * any node kind, inputs and CONST included), the selector folds through NOT / COPY / affine chains
+ * like any row input.  The node sits one level above the deepest of the selector's base and the
+ * candidates, counts one bootstrap (tfhe_amd_circuit_info) and one row
+ * (tfhe_amd_circuit_level_sizes), and shares its level's one key-switch launch; the select rows of
+ * a level run as a pack, a box fill per distinct p and one rows launch of the blind rotation of
+ * their own, after the level's other rows.  TFHE_AMD_E_ARG (nothing added) for another p, a null
+ * cand or any wire not yet defined.
+ * tfhe_amd_circuit_node reports kind 1, gate code -5, the selector's c0, s in coefficients[0] and
+ * sel in inputs[0]; tfhe_amd_circuit_select_node returns p, the candidates (cand[16], -1 beyond p)
+ * and c0, and TFHE_AMD_E_ARG for any other node.  tfhe_amd_circuit_select_count: the number of
+ * select nodes.
+ * tfhe_amd_circuit_lut2: a function of two 2-bit digits x, y (p = 4 boxes of tfhe_amd_lut_fill's
+ * convention) in two rotations: one many-LUT node on x with (log_nu, n_out) = (2, 4) whose output j
+ * is m -> values[4 j + m] (tfhe_amd_lut_fill_many(tv, 4, 2, 4, values)), then a select node over its
+ * four wires driven by y.  Returns the wire of values[4 y + x] (five wires are added).
+ * A circuit with a select node needs a packing key at run time: tfhe_amd_circuit_run_pk_dev is
+ * tfhe_amd_circuit_run_dev with the key, whose digit and accumulator scratch the select rows use
+ * (shared with, and ordered against, every other call on the key).  TFHE_AMD_E_ARG for a null key, a
+ * key on another device and a context without bootstrapping or key-switching key.
+ * tfhe_amd_circuit_run_dev and both tfhe_amd_multi_circuit_run_* forms return TFHE_AMD_E_ARG for a
+ * circuit that holds a select node, before anything is launched (packing keys have no replicas);
+ * a circuit without one behaves the same through either run form. */
+int tfhe_amd_circuit_select(TfheAmdCircuit *c, int p, const int *cand, int32_t c0, int32_t s, int sel);
+int tfhe_amd_circuit_select_node(const TfheAmdCircuit *c, int w, int *p, int cand[16], int32_t *c0);
+int tfhe_amd_circuit_select_count(const TfheAmdCircuit *c);
+int tfhe_amd_circuit_lut2(TfheAmdCircuit *c, const int32_t values[16], int x, int y);
+int tfhe_amd_circuit_run_pk_dev(TfheAmdContext *ctx, TfheAmdPackKey *pack_key, TfheAmdCircuit *c, int B,
+                                int32_t *wires_a, int32_t *wires_b, void *stream);
 /* integer builders over little-endian bit vectors of wire ids (Cipher.cpp's layout):
  * ripple-carry add (XOR3 / MAJ full adders, depth nbits; carry_in may be -1) -> carry wire;
  * subtract a - b -> carry wire; parallel-prefix add (depth 2 + log2 nbits) -> carry wire;

@@ -96,9 +96,18 @@ def main():
     short = lambda n: re.sub(r"\(anonymous namespace\)::|tfhe_amd::|^void ", "", names[n])
 
     # The gate kernels gained a trailing template flag (the tlwe form, false for every instantiation
-    # the parent has): a tree kernel is matched with the parent's by its name without that flag.
+    # the parent has); later the rows kernels gained the same flag and a trailing kernel argument (the
+    # accumulator samples, null in those instantiations): a tree kernel is matched with the parent's by
+    # its name, or by its name without the flag (and that argument) where the parent has no kernel of
+    # the full name.
+    parent_names = {short(n) for n in rp}
+
     def key(n):
-        return re.sub(r"^(k_blind_rotate_v(?:6p?|4)<[^>]*), false>", r"\1>", short(n))
+        k = short(n)
+        if k in parent_names:
+            return k
+        k = re.sub(r"^(k_blind_rotate_v(?:6p?|4)(?:_rows)?<[^>]*), false>", r"\1>", k)
+        return k if k in parent_names else re.sub(r"^(k_blind_rotate_v(?:6|4)_rows<.*), int const\*\)$", r"\1)", k)
     by_key = {short(n): n for n in rp}
     rt_all = rt
     rp = {n: rp[by_key[key(n)]] for n in rt if key(n) in by_key}       # parent figures under the tree's symbol

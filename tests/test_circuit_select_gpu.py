@@ -1,0 +1,512 @@
+"""Select nodes of the circuit engine on the GPU (tfhe_amd_circuit_select, tfhe_amd_circuit_lut2,
+tfhe_amd_circuit_run_pk_dev): every test compares all 501 words of every wire of
+every instance with the node-by-node evaluation of tests/select_dag_oracle.py, which folds nothing.
+Results are bit-exact: there is no tolerance.  Inputs, tables and the packing key are uniformly random
+words where decoding is not the point (the GPU and the oracle are exact integer maps); the lut2 case
+runs real ciphertexts through a generated packing key and decodes.  Launch thresholds are taken
+from the device's compute-unit count.  (tfhe_amd_last_kernels lists every launch name once, in the order
+of first launch.)"""
+import ctypes
+import time
+
+import numpy as np
+import pytest
+
+import acc_oracle as AO
+import dag_oracle as DO
+import guard_cases as G
+import lut_oracle as LO
+import oracle_ctypes as O
+import select_dag_oracle as SO
+import tfhe_amd as T
+
+pytestmark = pytest.mark.gpu
+
+N, n_lwe = 1024, 500
+E_ARG = -1
+E4 = 1 << 30
+PACK_MAX = 512                   # params.h kPackMaxBatch: outputs per pack launch pair
+DIGITS, PACK, FILL = "k_pack_digits_rows", "k_pack_v4", "k_tlwe_box_fill"
+LDS, REG = "k_blind_rotate_v6_rows(tlwe+lds-rotation)", "k_blind_rotate_v6_rows(tlwe+reg-rotation)"
+GUARD = "k_blind_rotate_v4_rows(tlwe+guard)"
+EXACT = "k_blind_rotate_v4_rows(tlwe)"
+
+
+def _rand32(rng, shape):
+    return rng.integers(-2**31, 2**31, shape, dtype=np.int64).astype(np.int32)
+
+
+def _cus():
+    import torch
+    assert torch.cuda.is_available(), "gpu tests need a GPU"
+    return int(torch.cuda.get_device_properties(0).multi_processor_count)
+
+
+_cache = {}
+
+
+def _random_pack_key(ctx):
+    if "rand" not in _cache:
+        words = _rand32(np.random.default_rng(3903), (n_lwe, 6, 2, N))
+        _cache["rand"] = (words, ctx.pack_key_import(words))
+    return _cache["rand"]
+
+
+def _inputs(seed, ins, B):
+    rng = np.random.default_rng([int(seed), int(B)])
+    return {w: (_rand32(rng, (B, n_lwe)), _rand32(rng, B)) for w in ins}
+
+
+def _wires(C, enc, B, n_w=None):
+    """the wire arrays with the inputs filled, complete before a context's own stream may touch them"""
+    import torch
+    n_w = C.info()["wires"] if n_w is None else n_w
+    wa = torch.zeros((n_w, B, n_lwe), dtype=torch.int32, device="cuda")
+    wb = torch.zeros((n_w, B), dtype=torch.int32, device="cuda")
+    for w, (a, b) in enc.items():
+        wa[w] = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        wb[w] = torch.from_numpy(np.ascontiguousarray(b)).cuda()
+    torch.cuda.synchronize()
+    return wa, wb
+
+
+def _run(ctx, pkey, C, enc, B, n_w=None):
+    wa, wb = _wires(C, enc, B, n_w)
+    C.run_dev(ctx, B, wa, wb, pack_key=pkey)
+    kern = ctx.last_kernels()
+    ctx.sync()
+    return wa.cpu().numpy(), wb.cpu().numpy(), kern
+
+
+def _check_wires(C, W, ha, hb, what):
+    """every wire, every instance, all 501 words"""
+    assert len(W) == ha.shape[0] == hb.shape[0], what
+    bad = [w for w in range(ha.shape[0]) if not (np.array_equal(ha[w], W[w][0]) and np.array_equal(hb[w], W[w][1]))]
+    if bad:
+        raise AssertionError(f"{what}: {len(bad)} of {len(W)} wires differ from the oracle; the first: "
+                             f"{[(w, C.node(w)) for w in bad[:6]]}")
+
+
+def _oracle(C, okey, enc, B, words, what, known=None):
+    t = time.time()
+    W = SO.eval_circuit(C, okey, enc, B, pack_key=words, known=known)
+    print(f"select_dag_oracle {what}: {C.info()['bootstraps'] * B} bootstraps, {time.time() - t:.2f} s")
+    return W
+
+
+def _in_order(kern, names):
+    """the names appear in kern in this order (other launches may lie between them)"""
+    at = 0
+    for name in names:
+        assert name in kern[at:], (name, kern)
+        at = kern.index(name, at) + 1
+
+
+# ------------------------------------------------------------------ 1. smallest shapes
+
+@pytest.mark.parametrize("p,B", [(2, 1), (2, 3), (4, 1), (4, 3), (16, 1)])
+def test_one_select_node(ctx, okey, p, B):
+    """one select node over input wires: LDS rotation, split pack, small key switch; the level's
+    launches, all of them, in order"""
+    words, pkey = _random_pack_key(ctx)
+    C = T.Circuit()
+    ins = C.inputs(p + 1)
+    w = C.select(ins[:p], ins[p], c0=E4 if p == 2 else 0)
+    enc = _inputs(1000 + p, ins, B)
+    W = _oracle(C, okey, enc, B, words, f"one node p = {p}, B = {B}")
+    ha, hb, kern = _run(ctx, pkey, C, enc, B)
+    _check_wires(C, W, ha, hb, f"one node p = {p}, B = {B}")
+    assert kern == [DIGITS, PACK + "(split)", FILL, LDS, GUARD, "k_keyswitch_small"], kern
+    C.close()
+
+
+# ------------------------------------------------------------------ 2. a mixed level, 5. guard at 0, 6. exact kernel
+
+def _mixed(okey, words, B=3):
+    """SO.mixed_circuit with its inputs and oracle wires, once per process"""
+    if "mixed" not in _cache:
+        C, ins, sels, others = SO.mixed_circuit()
+        enc = _inputs(2000, ins, B)
+        _cache["mixed"] = (C, ins, sels, enc, _oracle(C, okey, enc, B, words, f"mixed level, B = {B}"))
+    return _cache["mixed"]
+
+
+def test_mixed_level(ctx, okey):
+    """gate rows, a MUX pair, a LUT row, a many-LUT row and select rows of p = 2, 4, 2 in one level: the
+    select rows run behind the level's rows launch with one box fill per p, before its one key switch;
+    a second level reads the select outputs as selector, as candidate and through NOT / affine"""
+    words, pkey = _random_pack_key(ctx)
+    C, ins, sels, enc, W = _mixed(okey, words)
+    assert C.level_sizes() == [0, 9, 4]
+    ha, hb, kern = _run(ctx, pkey, C, enc, 3)
+    _check_wires(C, W, ha, hb, "mixed level, B = 3")
+    # level 0's bootstrap-free nodes; level 1: its rows, its select rows, its key switch (30 outputs);
+    # level 2 adds the names of its own form (its select rows repeat level 1's)
+    want = ["k_circuit_linear", "k_blind_rotate_v6_rows(lut-many+lds-rotation)", "k_blind_rotate_v4_rows(lut-many+guard)",
+            DIGITS, PACK + "(split)", FILL, LDS, GUARD, "k_keyswitch_v5", "k_blind_rotate_v6_rows(lut+lds-rotation)",
+            "k_blind_rotate_v4_rows(lut+guard)", "k_keyswitch_small"]
+    assert len(kern) == len(want) and all(k == w or (w == "k_keyswitch_v5" and k.startswith(w))
+                                          for k, w in zip(kern, want)), kern
+
+
+def test_guard_threshold_zero_recomputes_every_row(ctx, okey):
+    """threshold 0: every select ciphertext is recomputed by the exact tlwe rows kernel from the same
+    accumulator, to the same words; the counter counts the select rows x B and the other rows x B"""
+    words, pkey = _random_pack_key(ctx)
+    C, ins, sels, enc, W = _mixed(okey, words)
+    try:
+        T.set_guard_threshold(0.0)
+        ctx.guard_stats(reset=True)
+        ha, hb, kern = _run(ctx, pkey, C, enc, 3)
+        _, recomputed = ctx.guard_stats(reset=True)
+    finally:
+        T.set_guard_threshold(0.125)
+    _check_wires(C, W, ha, hb, "mixed level, B = 3, guard threshold 0")
+    assert GUARD in kern, kern
+    assert recomputed == C.info()["bootstraps"] * 3 == (5 + 8) * 3, recomputed
+
+
+def test_exact_kernel_generation(ctx, okey):
+    words, pkey = _random_pack_key(ctx)
+    C, ins, sels, enc, W = _mixed(okey, words)
+    try:
+        T.select_kernel(4)
+        ha, hb, kern = _run(ctx, pkey, C, enc, 3)
+    finally:
+        T.select_kernel(0)
+    _check_wires(C, W, ha, hb, "mixed level, B = 3, select_kernel(4)")
+    assert EXACT in kern and "k_blind_rotate_v4_rows(lut-many)" in kern, kern
+    assert not any("v6" in k or "guard" in k for k in kern), kern
+
+
+# ------------------------------------------------------------------ 3. aliasing corners
+
+def test_aliasing_corners(ctx, okey):
+    """one wire in every candidate slot; the selector also a candidate; a CONST and an input wire as
+    candidates; selectors that fold to the trivial sample (s = 0, and an affine chain of scale 0)"""
+    words, pkey = _random_pack_key(ctx)
+    rng = np.random.default_rng(3000)
+    word = lambda: int(rng.integers(-2**31, 2**31))
+    C = T.Circuit()
+    ins = C.inputs(3)
+    a, b, c = ins
+    k = C.gate("CONST", 1)
+    C.select([a] * 8, b, c0=word())
+    C.select([a, b], b, c0=E4)
+    C.select([k, a, c, k], c, c0=word(), s=3)
+    C.select([a, b], c, c0=word(), s=0)
+    C.select([b, c], C.affine(word(), 1 << 16, C.affine(word(), 1 << 16, a)), c0=word())
+    C.select([c, a, b, c], k, c0=word())
+    assert C.level_sizes() == [0, 6]
+    enc = _inputs(3001, ins, 3)
+    W = _oracle(C, okey, enc, 3, words, "aliasing corners")
+    ha, hb, kern = _run(ctx, pkey, C, enc, 3)
+    _check_wires(C, W, ha, hb, "aliasing corners")
+    assert kern[:6] == ["k_circuit_linear", DIGITS, PACK + "(split)", FILL, LDS, GUARD], kern   # level 0: CONST, affine
+    assert len(kern) == 7 and kern[6].startswith("k_keyswitch"), kern
+    C.close()
+
+
+# ------------------------------------------------------------------ 4. seams
+
+def _level_of_selects(nsel, ps, seed):
+    """one level of nsel select rows over 6 input wires, p cycling through ps; a NAND behind the last"""
+    rng = np.random.default_rng(seed)
+    C = T.Circuit()
+    ins = C.inputs(6)
+    out = []
+    for r in range(nsel):
+        p = ps[r % len(ps)]
+        out.append(C.select([int(x) for x in rng.choice(ins, p)], int(rng.choice(ins)), c0=int(rng.integers(-2**31, 2**31)),
+                            s=int(rng.choice([1, -1, 3]))))
+    C.gate("NAND", out[-1], ins[0])
+    return C, ins
+
+
+def _seam(ctx, okey, nsel, B, ps, seed, what):
+    words, pkey = _random_pack_key(ctx)
+    C, ins = _level_of_selects(nsel, ps, seed)
+    assert C.level_sizes() == [0, nsel, 1]
+    enc = _inputs(seed, ins, B)
+    W = _oracle(C, okey, enc, B, words, what)
+    ha, hb, kern = _run(ctx, pkey, C, enc, B)
+    _check_wires(C, W, ha, hb, what)
+    C.close()
+    return kern
+
+
+def test_seam_pack_batches(ctx, okey):
+    """nsel B = kPackMaxBatch + 1: the second pack batch (one output) reuses the digit scratch"""
+    nsel, B = 3, (PACK_MAX + 1) // 3
+    assert nsel * B == PACK_MAX + 1
+    kern = _seam(ctx, okey, nsel, B, [2], 4001, f"pack seam, {nsel} rows x B = {B}")
+    assert kern[0] == DIGITS and PACK + "(split)" in kern and FILL in kern, kern      # the batch of one output is split
+    if 2 * _cus() // PACK_MAX < 2:                                                    # pack_split: the full batch is not
+        assert kern[1] == PACK, kern
+
+
+def test_seam_register_rotation(ctx, okey):
+    """select rows x B just above one workgroup per compute unit: the register rotation; p = 4 and 2"""
+    cus = _cus()
+    nsel = 4
+    B = cus // nsel + 1
+    kern = _seam(ctx, okey, nsel, B, [4, 2], 4002, f"register rotation, {nsel} rows x B = {B} on {cus} CUs")
+    assert REG in kern and LDS not in kern and FILL in kern, kern
+
+
+def test_seam_second_rotation_launch(ctx, okey):
+    """select rows x B = 4 CUs + 3: the rotation takes two launches and the second (3 workgroups, LDS
+    rotation) starts inside the instances of the level's last select row"""
+    total = 4 * _cus() + 3
+    nsel = next((r for r in range(3, 64) if total % r == 0), 1)
+    B = total // nsel
+    kern = _seam(ctx, okey, nsel, B, [2], 4003, f"rotation seam, {nsel} rows x B = {B}")
+    _in_order(kern, [DIGITS, FILL, REG, LDS, GUARD])
+
+
+# ------------------------------------------------------------------ 5. guard: a partly flagged level
+
+def test_guard_partly_flagged_select_rows(keyset):
+    """The hostile key of tests/guard_cases.py (head-250), two select rows, B = 5.  The packing key is
+    all zeros and every candidate's body is 1/8, so each accumulator is the constant polynomial pair
+    (0, (1/8, ..., 1/8)) — constant polynomials are what the fp64 steps get wrong against the constant
+    key polynomials — and the selectors are input wires: dirty at (row 0, k = 2) and
+    (row 1, k = 4), clean real-step ones at (0, 0) and (1, 1), fillers elsewhere.  Every dirty selector
+    placed is one the unguarded fp64 steps get wrong from that accumulator on this GPU.  All words equal
+    the oracle and exactly the dirty slots are recomputed."""
+    import torch
+    bk = G.head_key(keyset.bk)
+    okey = O.OracleKey(bk, keyset.ksk, use_ntt=True)
+    hctx = T.Context(bk, keyset.ksk, device=0)
+    words = np.zeros((n_lwe, 6, 2, N), np.int32)
+    pkey = hctx.pack_key_import(words)
+    try:
+        rng = np.random.default_rng(20261)
+        cand = G.dirty(rng, 16)
+        tv = np.full(N, G.MU, np.int32)
+        start = np.zeros((16, 2, N), np.int32)
+        start[:, 1] = np.stack([O.mul_by_xai((2 * N - int(e)) % (2 * N), tv) for e in LO.modswitch_2n(cand[1])])
+        bara = np.ascontiguousarray(LO.modswitch_2n(cand[0]))
+        d_acc = torch.from_numpy(start.copy()).cuda()
+        hctx.blind_rotate_dev(d_acc, torch.from_numpy(bara).cuda(), n_lwe)   # the raw fp64 steps, no guard
+        hctx.sync()
+        raw = d_acc.cpu().numpy()
+        exact = start.copy()
+        for k in range(16):
+            O.lib().orc_blind_rotate(O._p(exact[k].reshape(2 * N)), ctypes.c_void_p(okey.h), O._p(bara[k]), n_lwe)
+        wrong = (raw[:, 0] != exact[:, 0]).any(axis=1) | (raw[:, 1, 0] != exact[:, 1, 0])
+        print(f"qualified pool (select rows): {int(wrong.sum())} of {wrong.size} candidates wrong unguarded")
+        if 2 * int(wrong.sum()) < wrong.size:
+            pytest.fail(f"{int(wrong.sum())} of {wrong.size} dirty candidates come out wrong unguarded: the pool is too thin")
+        pool = (cand[0][wrong], cand[1][wrong])
+        B, dirty_at, real_at = 5, [(0, 2), (1, 4)], [(0, 0), (1, 1)]
+        x = G.batch(np.random.default_rng(146), 2 * B, [r * B + k for r, k in dirty_at], [r * B + k for r, k in real_at],
+                    pool)
+        C = T.Circuit()
+        ins = C.inputs(4)
+        sel0, sel1, c0, c1 = ins
+        C.select([c0, c1], sel0)
+        C.select([c1, c0, c0, c1], sel1)
+        body = (np.zeros((B, n_lwe), np.int32), np.full(B, G.MU, np.int32))
+        enc = {sel0: (x[0][:B], x[1][:B]), sel1: (x[0][B:], x[1][B:]), c0: body, c1: body}
+        W = SO.eval_circuit(C, okey, enc, B, pack_key=words)
+        hctx.guard_stats(reset=True)
+        ha, hb, kern = _run(hctx, pkey, C, enc, B)
+        dist, redo = hctx.guard_stats(reset=True)
+        print(f"select rows partly flagged: recomputed {redo} (dirty {len(dirty_at)}), distance {dist:.4f}, kernels {kern}")
+        _check_wires(C, W, ha, hb, "partly flagged select rows")
+        assert kern[:5] == [DIGITS, PACK + "(split)", FILL, LDS, GUARD], kern
+        assert redo == len(dirty_at), redo
+        assert dist >= 0.125
+        C.close()
+    finally:
+        pkey.close()
+        hctx.close()
+
+
+# ------------------------------------------------------------------ 7. lifecycle, run forms
+
+def test_the_run_forms_without_a_pack_key_refuse_a_select_node(ctx, okey, keyset):
+    """tfhe_amd_circuit_run_dev and both tfhe_amd_multi_circuit_run_* forms: E_ARG before anything is
+    launched (no kernel in the trace, no wire written); a null key too; and a circuit without a select
+    node gives the same words through either run form"""
+    words, pkey = _random_pack_key(ctx)
+    B = 2
+    C = T.Circuit()
+    ins = C.inputs(3)
+    g = C.gate("NAND", ins[0], ins[1])
+    enc = _inputs(7000, ins, B)
+    ha0, hb0, kern0 = _run(ctx, None, C, enc, B)
+    ha1, hb1, kern1 = _run(ctx, pkey, C, enc, B)
+    assert np.array_equal(ha0, ha1) and np.array_equal(hb0, hb1) and kern0 == kern1 and len(kern0) == 3
+    _check_wires(C, DO.eval_circuit(C, okey, enc, B), ha1, hb1, "select-free circuit through run_pk_dev")
+    s = C.select([g, ins[2]], ins[0])
+    wa, wb = _wires(C, enc, B)
+    lib = T.lib
+    assert lib.tfhe_amd_circuit_run_dev(ctx.h, C.h, B, wa.data_ptr(), wb.data_ptr(), None) == E_ARG
+    assert ctx.last_kernels() == []
+    assert lib.tfhe_amd_circuit_run_pk_dev(ctx.h, None, C.h, B, wa.data_ptr(), wb.data_ptr(), None) == E_ARG
+    ctx.sync()
+    assert not wa[g].any() and not wa[s].any() and not wb[s].any()
+    m = T.MultiContext(keyset.bk, keyset.ksk, [0])
+    try:
+        with pytest.raises(T.TfheAmdError, match="code -1"):
+            m.circuit_dev(C, [(wa, wb)])
+        with pytest.raises(T.TfheAmdError, match="code -1"):
+            m.circuit_host(C, B, ins, np.stack([enc[w][0] for w in ins]), np.stack([enc[w][1] for w in ins]), [s])
+        m.sync()
+    finally:
+        m.close()
+    assert not wa[g].any() and not wa[s].any()
+    C.close()
+
+
+def test_the_circuit_grows_by_a_select_node_after_a_run(ctx, okey):
+    words, pkey = _random_pack_key(ctx)
+    B = 3
+    C, ins = _level_of_selects(2, [2, 4], 7001)
+    enc = _inputs(7001, ins, B)
+    W = _oracle(C, okey, enc, B, words, "lifecycle, before the growth")
+    ha, hb, _ = _run(ctx, pkey, C, enc, B)
+    _check_wires(C, W, ha, hb, "lifecycle, before the growth")
+    assert C.state_count() == 1
+    n_w = len(W)
+    new = C.select([n_w - 1, n_w - 2, ins[0], n_w - 3], n_w - 2)       # reads the select outputs and the NAND
+    assert C.info()["wires"] == n_w + 1 and C.state_count() == 0
+    W2 = _oracle(C, okey, enc, B, words, "lifecycle, grown by a select node", known=W)
+    ha, hb, _ = _run(ctx, pkey, C, enc, B)
+    _check_wires(C, W2, ha, hb, "lifecycle, grown by a select node")
+    C.select([new, new], ins[1], c0=E4)                                # no call that compiles before the run
+    ha, hb, _ = _run(ctx, pkey, C, enc, B, n_w=n_w + 2)
+    _check_wires(C, _oracle(C, okey, enc, B, words, "lifecycle, grown twice", known=W2), ha, hb, "lifecycle, grown twice")
+    C.close()
+
+
+def test_two_streams_across_a_scratch_regrowth(ctx, okey):
+    """B = 1 on one stream, then B = 4 on another with no host sync in between, on a fresh packing key:
+    the second run regrows the key's digit and accumulator scratch (and the circuit's u scratch) and is
+    ordered behind the first"""
+    import torch
+    words = _rand32(np.random.default_rng(7002), (n_lwe, 6, 2, N))
+    pkey = ctx.pack_key_import(words)
+    try:
+        C, ins = _level_of_selects(2, [4, 2], 7003)
+        jobs = []
+        for B in (1, 4):
+            enc = _inputs(7003, ins, B)
+            jobs.append((B, enc, _wires(C, enc, B), torch.cuda.Stream()))
+        for B, enc, (wa, wb), st in jobs:
+            C.run_dev(ctx, B, wa, wb, stream=st.cuda_stream, pack_key=pkey)
+        torch.cuda.synchronize()
+        for B, enc, (wa, wb), st in jobs:
+            W = _oracle(C, okey, enc, B, words, f"two streams, B = {B}")
+            _check_wires(C, W, wa.cpu().numpy(), wb.cpu().numpy(), f"two streams, B = {B}")
+        C.close()
+    finally:
+        pkey.close()
+
+
+def test_one_circuit_on_two_contexts_each_with_its_own_pack_key(ctx, okey, keyset):
+    words, pkey = _random_pack_key(ctx)
+    words2 = _rand32(np.random.default_rng(7004), (n_lwe, 6, 2, N))
+    ctx2 = T.Context(keyset.bk, keyset.ksk, device=0)
+    pkey2 = ctx2.pack_key_import(words2)
+    try:
+        B = 2
+        C, ins = _level_of_selects(2, [2, 4], 7005)
+        enc = _inputs(7005, ins, B)
+        w1, w2 = _wires(C, enc, B), _wires(C, enc, B)
+        C.run_dev(ctx, B, *w1, pack_key=pkey)
+        C.run_dev(ctx2, B, *w2, pack_key=pkey2)
+        ctx.sync()
+        ctx2.sync()
+        assert C.state_count() == 2
+        _check_wires(C, _oracle(C, okey, enc, B, words, "two contexts, first"), w1[0].cpu().numpy(), w1[1].cpu().numpy(),
+                     "two contexts, first")
+        _check_wires(C, _oracle(C, okey, enc, B, words2, "two contexts, second"), w2[0].cpu().numpy(),
+                     w2[1].cpu().numpy(), "two contexts, second")
+        C.close()
+    finally:
+        pkey2.close()
+        ctx2.close()
+
+
+# ------------------------------------------------------------------ 8. lut2
+
+def test_lut2_reproduces_the_cpu_decode_case(ctx, okey, keyset):
+    """the case of tests/test_circuit_select.py (B = 32, two fresh p = 4 digits, a random table): the
+    GPU's words are the oracle's on every wire, so the output decodes to values[4 y + x] as well"""
+    c = SO.lut2_case(keyset, okey)
+    pkey = ctx.pack_key_import(c["key"])
+    try:
+        ha, hb, kern = _run(ctx, pkey, c["C"], c["enc"], c["B"])
+        _check_wires(c["C"], c["W"], ha, hb, "lut2 decode case")
+        out = c["out"]
+        assert np.array_equal(T.lut_decode(keyset.phase(ha[out], hb[out]), 4), c["f"][c["y"], c["x"]])
+        _in_order(kern, ["k_blind_rotate_v6_rows(lut-many+lds-rotation)", DIGITS, PACK + "(split)", FILL, LDS, GUARD])
+    finally:
+        pkey.close()
+
+
+# ------------------------------------------------------------------ 9. a short seeded random mix
+
+MIX_SEEDS = [9001, 9002, 9003]           # a seed that once failed stays in the list
+
+
+def random_mix(seed):
+    """A DAG of three levels from np.random.default_rng(seed) alone: every level draws gate rows (a MUX
+    among them), LUT rows, many-LUT rows and select rows of two of the p in {2, 4, 8, 16} (the oracle
+    converts the packing key once per level and p) over any earlier wires, then a few NOT / affine nodes; tables and constants are uniformly random words, coefficients small
+    or random.  -> (Circuit, input wires)"""
+    rng = np.random.default_rng(int(seed))
+    word = lambda: int(rng.integers(-2**31, 2**31))
+    coef = lambda: int(rng.choice([1, -1, 2, 3, 0, 1 << 16])) if rng.random() < 0.7 else word()
+    tv = lambda: rng.integers(-2**31, 2**31, N, dtype=np.int64).astype(np.int32)
+    C = T.Circuit()
+    ins = C.inputs(int(rng.integers(5, 8)))
+    pool, front = list(ins), list(ins)
+    pick = lambda k: [int(front[int(rng.integers(len(front)))])] + [int(x) for x in rng.choice(pool, k - 1)]
+    for level in range(3):
+        new = []
+        ps = rng.choice([2, 4, 8, 16], 2, replace=False)
+        for kind in ["gate", "mux", "lut", "many", "select", "select"] + list(rng.choice(["gate", "lut", "many", "select"], 3)):
+            if kind == "gate":
+                a, b = pick(2)
+                new.append(C.gate(str(rng.choice(["NAND", "XOR", "ORNY"])), a, b))
+            elif kind == "mux":
+                new.append(C.gate("MUX", *pick(3)))
+            elif kind == "lut":
+                a, b, c = pick(3)
+                new.append(C.lut(C.lut_table(tv()), word(), coef() or 1, a, coef(), b, coef(), c))
+            elif kind == "many":
+                log_nu, n_out = [(1, 2), (2, 3), (4, 16)][int(rng.integers(3))]
+                a, b = pick(2)
+                w = C.lut_many(C.lut_table(tv()), log_nu, n_out, word(), coef() or 1, a, coef(), b)
+                new += list(range(w, w + n_out))
+            else:
+                p = int(rng.choice(ps))
+                sel = pick(1)[0]
+                cand = [int(x) for x in rng.choice(pool, p)]
+                if rng.random() < 0.5:
+                    cand[int(rng.integers(p))] = pick(1)[0]
+                new.append(C.select(cand, sel, c0=word(), s=coef()))
+        for _ in range(int(rng.integers(1, 4))):
+            x = int(rng.choice(new))
+            new.append(C.gate("NOT", x) if rng.random() < 0.4 else C.affine(word(), coef(), x))
+        pool += new
+        front = new
+    return C, ins
+
+
+@pytest.mark.parametrize("seed,B", [(s, 3) for s in MIX_SEEDS] + [(MIX_SEEDS[0], 1)])
+def test_random_mix(ctx, okey, seed, B):
+    words, pkey = _random_pack_key(ctx)
+    what = f"random mix seed {seed}, B = {B}"
+    C, ins = random_mix(seed)
+    assert C.select_count() >= 6 and C.info()["depth"] >= 3, what
+    enc = _inputs(seed, ins, B)
+    W = _oracle(C, okey, enc, B, words, what)
+    ha, hb, kern = _run(ctx, pkey, C, enc, B)
+    _check_wires(C, W, ha, hb, what)
+    _in_order(kern, [DIGITS, PACK + "(split)", FILL, LDS, GUARD])
+    C.close()
