@@ -399,6 +399,75 @@ __global__ __launch_bounds__(kV4Threads, 2) void k_tgsw_cmux_v4(V4Args g, TgswCm
         out[j] = (int32_t)(word(d0, j) + (live ? sh.E[j >> kLogN][j & (kN - 1)] : 0u));
 }
 
+// Leveled automaton, one step over one input bit (engine.h TgswDfaStep): workgroup w
+// computes state st = live[w mod n_live] of query q = w / n_live,
+//   out = d0 + C_sel (x) (d1 - d0 + 2^11 on every word), d_b = the sample of state next[st][b],
+// the XP path of cmux_v4 on the difference.  The 2^11 centres the decomposition's truncation (it
+// drops 12 bits of every word): the product reads only the digits, so nothing else changes.  The
+// operands come from the source buffer, the result goes to the destination buffer at the state's own
+// slot, and the two buffers are distinct: within a launch no workgroup reads what another writes.
+// FIRST: the operands are the final weights (rows = 1: the mask is zero).  LAST: the result (the
+// start state's) is extracted as in k_tgsw_lookup_v4 instead of being stored.
+// Every index read from device memory is wave-uniform and checked before an address is formed: a
+// state or transition outside [0, Q) ends the workgroup, a selector outside [0, count) and a state
+// with next0 == next1 (whose product is exactly zero) give out = d0, fin_index is clamped.
+template <bool FIRST, bool LAST>
+__global__ __launch_bounds__(kV4Threads, 2) void k_tgsw_dfa_v4(V4Args g, TgswDfaStep a) {
+    __shared__ V4Shared sh;
+    const int tid = threadIdx.x;
+    const int s = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int L = tid & 63;
+    const int w = blockIdx.x;
+    const int q = w / a.n_live;
+    if (q >= a.B) return;
+    const int st = tgsw_sel(a.live + (w - q * a.n_live));
+    if (st < 0 || st >= a.Q) return;
+    const int n0 = tgsw_sel(a.next + 2 * st), n1 = tgsw_sel(a.next + 2 * st + 1);
+    if (n0 < 0 || n0 >= a.Q || n1 < 0 || n1 >= a.Q) return;
+    int rows = 2;
+    const int32_t *base;
+    if constexpr (FIRST) {
+        int t = a.fin_index ? tgsw_sel(a.fin_index + q) : 0;
+        t = t < 0 ? 0 : t >= a.n_fin ? a.n_fin - 1 : t;
+        rows = a.fin_rows;
+        base = a.fin + (size_t)t * a.Q * rows * kN;
+    } else {
+        base = a.src + (size_t)q * a.Q * 2 * kN;
+    }
+    const int32_t *d0 = base + (size_t)n0 * rows * kN, *d1 = base + (size_t)n1 * rows * kN;
+    const int idx = tgsw_sel(a.sel + (size_t)q * a.sel_stride);
+    const bool live = n0 != n1 && idx >= 0 && idx < a.count;
+    // word j of an operand, j < 2 kN; rows = 1: the mask is zero and the body is the one row
+    auto word = [&](const int32_t *d, int j) -> uint32_t {
+        if (rows == 1 && j < kN) return 0u;
+        return (uint32_t)d[rows == 1 ? j - kN : j];
+    };
+    if (live) {
+        for (int j = tid; j < 2 * kN; j += kV4Threads)
+            e_store(sh.E[j >> kLogN], j & (kN - 1), word(d1, j) - word(d0, j) + (1u << 11));
+        __syncthreads();
+        cmux_v4<true>(sh, g, idx, 0, s, L);
+    }
+    if constexpr (!LAST) {
+        int32_t *out = a.dst + ((size_t)q * a.Q + st) * 2 * kN;
+        for (int j = tid; j < 2 * kN; j += kV4Threads)
+            out[j] = (int32_t)(word(d0, j) + (live ? sh.E[j >> kLogN][j & (kN - 1)] : 0u));
+    } else {
+        // each thread replaces the words it read: the sum as the periodic extension the extraction reads
+        for (int j = tid; j < 2 * kN; j += kV4Threads) {
+            uint32_t *E = sh.E[j >> kLogN];
+            const int k = j & (kN - 1);
+            e_store(E, k, word(d0, j) + (live ? E[k] : 0u));
+        }
+        __syncthreads();
+        for (int f = 0; f < a.n_out; ++f) {   // extraction at index f: a_j = E_a[(f - j) mod 2N], b = acc_b[f]
+            int32_t *uf = a.u_a + ((size_t)f * a.u_stride + q) * kN;
+            for (int j = tid; j < kN; j += kV4Threads) uf[j] = (int32_t)sh.E[0][(f - j) & (k2N - 1)];
+        }
+        if (tid < a.n_out) a.u_b[(size_t)tid * a.u_stride + q] = (int32_t)sh.E[1][tid];
+    }
+}
+
 unsigned brv10(unsigned x) {
     unsigned r = 0;
     for (int i = 0; i < kLogN; i++) { r = (r << 1) | (x & 1); x >>= 1; }
@@ -555,6 +624,28 @@ hipError_t launch_tgsw_cmux_v4(const DeviceKey &key, const uint32_t *set, int pa
         return hipErrorInvalidValue;
     trace_kernel(label ? label : "k_tgsw_cmux_v4");
     hipLaunchKernelGGL(k_tgsw_cmux_v4, dim3(pairs), dim3(kV4Threads), 0, s, g, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_tgsw_dfa_v4(const DeviceKey &key, const uint32_t *set, const TgswDfaStep &a, bool first, bool last,
+                              hipStream_t s) {
+    if (a.B <= 0) return hipSuccess;
+    V4Args g;
+    if (!tgsw_args(key, set, a.count, &g) || !a.sel || !a.next || !a.live || a.Q < 1 || a.Q > 64 || a.n_live < 1 ||
+        a.n_live > a.Q || (long)a.B * a.n_live > 0x7fffffffL)
+        return hipErrorInvalidValue;
+    if (first ? (!a.fin || a.n_fin < 1 || a.fin_rows < 1 || a.fin_rows > 2) : !a.src) return hipErrorInvalidValue;
+    if (last ? (a.n_live != 1 || !a.u_a || !a.u_b || a.n_out < 1 || a.n_out > 16 || a.u_stride < a.B)
+             : (!a.dst || a.dst == a.src))
+        return hipErrorInvalidValue;
+    trace_kernel(first ? (last ? "k_tgsw_dfa_v4(weights+extract)" : "k_tgsw_dfa_v4(weights)")
+                       : (last ? "k_tgsw_dfa_v4(extract)" : "k_tgsw_dfa_v4"));
+    with_flag(first, [&](auto fi) {
+        with_flag(last, [&](auto la) {
+            hipLaunchKernelGGL((k_tgsw_dfa_v4<decltype(fi)::value, decltype(la)::value>), dim3(a.B * a.n_live),
+                               dim3(kV4Threads), 0, s, g, a);
+        });
+    });
     return hipGetLastError();
 }
 

@@ -238,6 +238,33 @@ hipError_t launch_tgsw_lookup_v4(const DeviceKey &key, const uint32_t *set, cons
 // label: the name the launch trace gets (null: "k_tgsw_cmux_v4")
 hipError_t launch_tgsw_cmux_v4(const DeviceKey &key, const uint32_t *set, int pairs, const TgswCmux &a,
                                hipStream_t s, const char *label = nullptr);
+// One step of a leveled automaton (tgsw_dfa.cpp), one workgroup per (query q < B,
+// live state): for every s = live[k], k < n_live,
+//   dst[q][s] = d0 + C_sel[q sel_stride] (x) (d1 - d0 + 2^11 on every word), d_b = src[q][next[s][b]],
+// over state buffers [B][Q][2][kN] indexed by state id; src and dst are distinct buffers.  A state
+// with next[s][0] == next[s][1] and a selector outside [0, count) give dst = d0.
+// first: the operands are the final weights fin [n_fin][Q][fin_rows][kN] of table fin_index[q] (null:
+// 0; clamped into [0, n_fin)) instead of src; fin_rows = 1: the trivial sample (0, fin).
+// last: the result is not stored but extracted at the coefficients f < n_out into u sample
+// f u_stride + q (the lookup kernel's index rule); n_live is 1 then (the start state).
+struct TgswDfaStep {
+    int B = 0, count = 0, Q = 0;
+    const int32_t *sel = nullptr;
+    int sel_stride = 1;
+    const int32_t *next = nullptr;   // [Q][2]
+    const int32_t *live = nullptr;
+    int n_live = 0;
+    const int32_t *src = nullptr;
+    int32_t *dst = nullptr;
+    const int32_t *fin = nullptr;
+    int n_fin = 1, fin_rows = 1;
+    const int32_t *fin_index = nullptr;
+    int n_out = 1;
+    long u_stride = 0;
+    int32_t *u_a = nullptr, *u_b = nullptr;
+};
+hipError_t launch_tgsw_dfa_v4(const DeviceKey &key, const uint32_t *set, const TgswDfaStep &a, bool first, bool last,
+                              hipStream_t s);
 // count-taking forms of launch_bk_to_ntt / launch_bk_v1_to_v2 (the same kernels over `count` samples)
 hipError_t launch_tgsw_to_ntt(const int32_t *d_coef, uint32_t *d_ntt, const NttTables *d_tab, int count,
                               hipStream_t s);

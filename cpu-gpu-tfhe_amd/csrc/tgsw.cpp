@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "tgsw_internal.h"
 #include "../../include/tfhe_amd.h"
 
 using namespace tfhe_amd;
@@ -21,19 +22,6 @@ using namespace tfhe_amd;
             return TFHE_AMD_E_HIP;                                                \
         }                                                                         \
     } while (0)
-
-// `count` samples on `device` in the exact kernels' key layout (DeviceKey.bk_v2), 64 KB each, and
-// the CMux tree's scratch: two buffers the levels alternate between, shared by every lookup on
-// the set, so their reuse is ordered across streams like a context's extracted samples.
-struct TfheAmdTgsw {
-    int device = -1;
-    int count = 0;
-    uint32_t *v2 = nullptr;
-    std::mutex mu;
-    int32_t *tree = nullptr;
-    size_t tree_words = 0;
-    StreamFence fence;
-};
 
 namespace {
 
@@ -199,22 +187,6 @@ int cmux_in_frame(const ContextFrame &f, void *arg) {
     HIPCHK(launch_tgsw_cmux_v4(*f.key, j.set->v2, j.B, c, f.stream));
     return TFHE_AMD_OK;
 }
-
-// temporary device buffers of the host forms, freed on every path
-struct DevBufs {
-    std::vector<void *> p;
-    ~DevBufs() {
-        for (void *q : p) (void)hipFree(q);
-    }
-    template <class T>
-    hipError_t get(T **out, size_t words) {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, sizeof(T) * (words ? words : 1));
-        if (e == hipSuccess) p.push_back(q);
-        *out = static_cast<T *>(q);
-        return e;
-    }
-};
 
 struct HostLookupJob {
     TfheAmdContext *c;

@@ -149,6 +149,22 @@ def _load():
     for f in ("tfhe_amd_tgsw_lookup_woks_host", "tfhe_amd_tgsw_lookup_host"):
         getattr(L, f).argtypes = ([_VP, _VP, ctypes.c_int, ctypes.c_int, _I32P] + [ctypes.c_int] * 3 + [_I32P, _I32P]
                                   + [ctypes.c_int] * 2 + [_I32P, _I32P])
+    # leveled automata (tfhe_amd_dfa_*)
+    L.tfhe_amd_dfa_create.argtypes = [_VP, ctypes.c_int, ctypes.c_int, _I32P, ctypes.c_int, ctypes.POINTER(_VP)]
+    L.tfhe_amd_dfa_destroy.argtypes = [_VP]
+    L.tfhe_amd_dfa_info.argtypes = [_VP] + [ctypes.POINTER(ctypes.c_int)] * 4
+    L.tfhe_amd_dfa_live.argtypes = [_VP, ctypes.c_int, _I32P]
+    for f in ("tfhe_amd_dfa_run_woks_dev", "tfhe_amd_dfa_run_dev"):
+        getattr(L, f).argtypes = ([_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP,
+                                   ctypes.c_int, _VP, _VP, _VP])
+    for f in ("tfhe_amd_dfa_run_woks_host", "tfhe_amd_dfa_run_host"):
+        getattr(L, f).argtypes = ([_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _I32P, ctypes.c_int, ctypes.c_int, _I32P,
+                                   _I32P, ctypes.c_int, _I32P, _I32P])
+    L.tfhe_amd_dfa_build_compare.argtypes = [_I32P, ctypes.POINTER(ctypes.c_int), _I32P]
+    L.tfhe_amd_dfa_build_contains.argtypes = [ctypes.c_int, _I32P, _I32P, ctypes.POINTER(ctypes.c_int)]
+    L.tfhe_amd_dfa_build_at_least.argtypes = [ctypes.c_int, _I32P, ctypes.POINTER(ctypes.c_int)]
+    L.tfhe_amd_dfa_fin_fill.argtypes = [ctypes.c_int, ctypes.c_int, _I32P, _I32P]
+    L.tfhe_amd_dfa_simulate.argtypes = [ctypes.c_int, ctypes.c_int, _I32P, ctypes.c_int, _I32P]
     # packing key switch (tfhe_amd_pack_*)
     L.tfhe_amd_pack_key_generate.argtypes = [_VP, _I32P]
     L.tfhe_amd_tlwe_phase_polys.argtypes = [_VP, ctypes.c_int, _I32P, _I32P]
@@ -585,6 +601,106 @@ class TgswSet:
             pass
 
 
+class Dfa:
+    """TfheAmdDfa: a deterministic automaton over TGSW-encrypted bits on a context's device
+    (Context.dfa_create), or a host-only one (Dfa.host: device -1, inspection only); close() frees
+    it.  It does not depend on the context's lifetime."""
+
+    def __init__(self, h):
+        self.h = h
+        v = [ctypes.c_int() for _ in range(4)]
+        _check(lib.tfhe_amd_dfa_info(h, *[ctypes.byref(x) for x in v]), "dfa_info")
+        self.n_states, self.start, self.max_len, self.device = (x.value for x in v)
+
+    @classmethod
+    def _create(cls, ctx_h, next, start, max_len):
+        next = i32(next)
+        if next.ndim != 2 or next.shape[1] != 2:
+            raise TfheAmdError(f"next: need int32 [n_states][2], got {next.shape}")
+        h = _VP()
+        _check(lib.tfhe_amd_dfa_create(ctx_h, next.shape[0], int(start), _p(next), int(max_len), ctypes.byref(h)),
+               "dfa_create")
+        return cls(h.value)
+
+    @classmethod
+    def host(cls, next, start, max_len):
+        """tfhe_amd_dfa_create without a context: the live sets can be read, no run accepts it"""
+        return cls._create(None, next, start, max_len)
+
+    def live(self, step):
+        """tfhe_amd_dfa_live: the states reachable from the start state after `step` bits, ascending"""
+        out = np.zeros(self.n_states, np.int32)
+        n = lib.tfhe_amd_dfa_live(self.h, int(step), _p(out))
+        if n < 0:
+            raise TfheAmdError(f"dfa_live failed with code {n}")
+        return out[:n]
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.tfhe_amd_dfa_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+DFA_LT, DFA_EQ, DFA_GT, DFA_MID = 0, 1, 2, 3
+
+
+def _dfa_built(n, what):
+    if n < 0:
+        raise TfheAmdError(f"{what} failed with code {n}")
+    return n
+
+
+def dfa_compare():
+    """tfhe_amd_dfa_build_compare: x against y over the word x_{d-1}, y_{d-1}, ..., x_0, y_0 ->
+    (next [5][2], start, cls [5] of DFA_LT / DFA_EQ / DFA_GT / DFA_MID)"""
+    next, cls, start = np.zeros((5, 2), np.int32), np.zeros(5, np.int32), ctypes.c_int()
+    _dfa_built(lib.tfhe_amd_dfa_build_compare(_p(next), ctypes.byref(start), _p(cls)), "dfa_build_compare")
+    return next, start.value, cls
+
+
+def dfa_contains(pattern):
+    """tfhe_amd_dfa_build_contains: the KMP automaton of a bit pattern (first bit first) ->
+    (next [m + 1][2], start); state m: the word contains the pattern"""
+    pattern = i32(np.asarray(pattern).reshape(-1))
+    next, start = np.zeros((pattern.shape[0] + 1, 2), np.int32), ctypes.c_int()
+    _dfa_built(lib.tfhe_amd_dfa_build_contains(pattern.shape[0], _p(pattern), _p(next), ctypes.byref(start)),
+               "dfa_build_contains")
+    return next, start.value
+
+
+def dfa_at_least(t):
+    """tfhe_amd_dfa_build_at_least: a saturating count of ones -> (next [t + 1][2], start); state t:
+    at least t bits are set"""
+    t = int(t)
+    next, start = np.zeros((max(t, 0) + 1, 2), np.int32), ctypes.c_int()
+    _dfa_built(lib.tfhe_amd_dfa_build_at_least(t, _p(next), ctypes.byref(start)), "dfa_build_at_least")
+    return next, start.value
+
+
+def dfa_fin(values):
+    """tfhe_amd_dfa_fin_fill: values [n_states][n_out] Torus32 -> the plaintext final weights
+    [1][n_states][1][1024] (one table, fin_rows = 1)"""
+    values = i32(values)
+    if values.ndim == 1:
+        values = np.ascontiguousarray(values[:, None])
+    fin = np.zeros((1, values.shape[0], 1, N), np.int32)
+    _check(lib.tfhe_amd_dfa_fin_fill(values.shape[0], values.shape[1], _p(values), _p(fin)), "dfa_fin_fill")
+    return fin
+
+
+def dfa_simulate(next, start, bits):
+    """tfhe_amd_dfa_simulate: the state after the plain word bits (bit 0 first)"""
+    next, bits = i32(next), i32(np.asarray(bits).reshape(-1))
+    return _dfa_built(lib.tfhe_amd_dfa_simulate(next.shape[0], int(start), _p(next), bits.shape[0], _p(bits)),
+                      "dfa_simulate")
+
+
 class PackKey:
     """TfheAmdPackKey: the packing key imported to a context's device (Context.pack_key_import);
     close() frees it.  It does not depend on the context's lifetime."""
@@ -924,6 +1040,51 @@ class Context:
                                                 tab.data_ptr(), None if tab_index is None else tab_index.data_ptr(),
                                                 int(log_stride), n_out, out_a.data_ptr(), out_b.data_ptr(), stream),
                name)
+
+    # ---- leveled automata (tfhe_amd_dfa_*): a DFA over TGSW-encrypted bits, one CMux per step
+    def dfa_create(self, next, start, max_len):
+        """tfhe_amd_dfa_create: next [n_states][2] (dfa_compare, dfa_contains, dfa_at_least or the
+        caller's own) -> Dfa on this context's device, for words of up to max_len bits"""
+        return Dfa._create(self.h, next, start, max_len)
+
+    def dfa_run_host(self, tset, dfa, sel, fin, fin_index=None, n_out=1, woks=False):
+        """tfhe_amd_dfa_run[_woks]_host: sel [B][len] selector indices (bit 0 first), fin
+        [n_fin][n_states][fin_rows][1024] final weights -> (r_a [n_out][B][500], r_b [n_out][B]), or
+        with woks the extracted samples (u_a [n_out][B][1024], u_b [n_out][B])"""
+        sel = i32(sel); fin = i32(fin)
+        if sel.ndim != 2 or fin.ndim != 4 or fin.shape[1] != dfa.n_states or fin.shape[3] != N:
+            raise TfheAmdError(f"need sel [B][len] and fin [n_fin][{dfa.n_states}][fin_rows][1024], got {sel.shape}, "
+                               f"{fin.shape}")
+        B, length = sel.shape
+        n_fin, _, rows, _ = fin.shape
+        idx = None if fin_index is None else i32(fin_index)
+        if idx is not None and idx.shape != (B,):
+            raise TfheAmdError(f"fin_index: need one table index per query ({B}), got {idx.shape}")
+        n_out = int(n_out)
+        r_a = np.zeros((max(n_out, 1), B, N if woks else n_lwe), np.int32)
+        r_b = np.zeros((max(n_out, 1), B), np.int32)
+        name = "dfa_run" + ("_woks" if woks else "") + "_host"
+        _check(getattr(lib, "tfhe_amd_" + name)(self.h, tset.h, dfa.h, B, length, _p(sel), n_fin, rows, _p(fin),
+                                                _p(idx), n_out, _p(r_a), _p(r_b)), name)
+        return r_a, r_b
+
+    def dfa_run_dev(self, tset, dfa, sel, fin, out_a, out_b, fin_index=None, n_out=1, woks=False, stream=None):
+        """tfhe_amd_dfa_run[_woks]_dev on torch tensors (shapes as dfa_run_host); asynchronous"""
+        if sel is None or sel.dim() != 2 or fin is None or fin.dim() != 4:
+            raise TfheAmdError("need GPU tensors sel [B][len] and fin [n_fin][n_states][fin_rows][1024]")
+        B, length = sel.shape
+        n_fin, _, rows, _ = fin.shape
+        n_out = int(n_out)
+        named = [("sel", sel, (B, length)), ("fin", fin, (n_fin, dfa.n_states, rows, N)),
+                 ("out_a", out_a, (max(n_out, 1), B, N if woks else n_lwe)), ("out_b", out_b, (max(n_out, 1), B))]
+        if fin_index is not None:
+            named.append(("fin_index", fin_index, (B,)))
+        for name, t, shape in named:
+            self._dev_check(t, shape, name)
+        name = "dfa_run" + ("_woks" if woks else "") + "_dev"
+        _check(getattr(lib, "tfhe_amd_" + name)(self.h, tset.h, dfa.h, B, length, sel.data_ptr(), n_fin, rows,
+                                                fin.data_ptr(), None if fin_index is None else fin_index.data_ptr(),
+                                                n_out, out_a.data_ptr(), out_b.data_ptr(), stream), name)
 
     # ---- packing key switch (tfhe_amd_pack_*): computed LWE samples -> TLWE ciphertexts
     def pack_key_import(self, coef):

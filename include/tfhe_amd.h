@@ -370,6 +370,102 @@ int tfhe_amd_tgsw_lookup_host(TfheAmdContext *ctx, TfheAmdTgsw *set, int B, int 
                               const int32_t *tab_index, int log_stride, int n_out,
                               int32_t *res_a, int32_t *res_b);
 
+/* ---- Leveled automata: a deterministic automaton over client TGSW bits.
+ * The other leveled primitive: an automaton of Q states, a start state and transitions
+ * next[s * 2 + bit] reads a word of len bits that arrive as TGSW ciphertexts, at one exact CMux per
+ * live state and input bit and no bootstrap.  A function that reads its input bit-serially (compare
+ * two integers, find a pattern, count flags up to a threshold) is evaluated that way; the result is,
+ * after the key switch, an ordinary n = 500 sample that every gate, LUT row and select node can read.
+ * The same LIMIT as the lookup's: the bits must be the client's TGSW ciphertexts.
+ *
+ * Semantics.  Query q reads bit i (bit 0 first) from sample sel[q * len + i] of the set.  The final
+ * weights fin [n_fin][Q][fin_rows][1024] hold one polynomial per state (fin_rows = 1: plaintext
+ * Torus32 words, the trivial sample (0, fin); fin_rows = 2: TLWE samples (a, then b) from
+ * tfhe_amd_tlwe_encrypt_polys or tfhe_amd_pack_*); query q uses table fin_index[q] (NULL: table 0).
+ * The evaluation runs backwards over the word: ACC_len[s] = fin[s], and for j = len .. 1
+ *   ACC_{j-1}[s] = d0 + C_j (x) (d1 - d0 + 2^11 (1 + X + ... + X^1023) on both polynomials)
+ * with d_b = ACC_j[next[s][b]] and C_j the sample of bit j - 1, the exact product of the CMux gate.
+ * The 2^11 centres the gadget decomposition's truncation, whose mean would otherwise add up along
+ * the chain; the product reads only the digits, so nothing else changes.  The
+ * output ACC_0[start] has the phase fin[state reached after the whole word] plus noise; its
+ * coefficients 0 .. n_out - 1 (n_out <= 16) are extracted, function-major as in the lookup: the woks
+ * forms return u_a [n_out][B][1024], u_b [n_out][B], the other forms run ONE key switch over the
+ * n_out B samples into res_a [n_out][B][500], res_b [n_out][B].
+ * Step j computes only the states reachable from the start state after j - 1 bits (the live sets
+ * R_{j-1}, computed once at creation), and a state with next0 == next1 copies its operand: its
+ * product is exactly zero.
+ *
+ * tfhe_amd_dfa_create: an automaton on the context's device: the transitions and the live sets
+ *   R_0 .. R_{max_len - 1} uploaded once, and the state scratch of the runs (two buffers of Q TLWE
+ *   samples per query, grown on demand, at most 256 MiB: a larger batch runs in slices), shared by the
+ *   runs on the automaton and ordered across streams like a set's tree scratch.  Like a set it does
+ *   not depend on the context's lifetime and may be used with any context on the same device.
+ *   ctx = NULL makes a host-only automaton (device -1) that _info and _live read and every run
+ *   refuses; it touches no device.  1 <= n_states <= 64, 0 <= start < n_states, 1 <= max_len <= 1024
+ *   (one product adds a variance of 4 * 1024 * (2^20 / 12) * sigma_bk^2 = 1.85e-8, so 1024 steps give
+ *   a standard deviation of 4.4e-3, 1/32 over 7), every transition in [0, n_states); else
+ *   TFHE_AMD_E_ARG and *out = NULL.  Destroy waits for the device and takes NULL.
+ * tfhe_amd_dfa_info: any of n_states, start, max_len, device may be NULL.
+ * tfhe_amd_dfa_live: the number of states of R_step, 0 <= step <= max_len, written in ascending
+ *   order to states (at most n_states words; NULL: the count alone); TFHE_AMD_E_ARG otherwise.
+ *
+ * tfhe_amd_dfa_run_*: B queries of len bits, 1 <= len <= max_len.  The _dev forms take device arrays
+ * and are asynchronous on `stream`; every index they read is checked on the device before an address
+ * is formed: a selector outside [0, count) gives that step's result = the next[s][0] operand, a
+ * fin_index entry is clamped into [0, n_fin).  The _host forms stage through temporary device
+ * buffers, are synchronous and return TFHE_AMD_E_ARG for any selector or fin_index entry out of
+ * range, writing nothing.  TFHE_AMD_E_ARG also for B < 0, len outside [1, max_len], n_fin < 1,
+ * fin_rows outside {1, 2}, n_out outside [1, 16], null arrays with B > 0, a set or automaton on
+ * another device than the context's and, in the key-switched forms, a context without
+ * key-switching key; B = 0 returns TFHE_AMD_OK.
+ * There is no fp64 form: tfhe_amd_select_kernel and the exactness guard do not apply.
+ * There is one launch per input bit; tfhe_amd_last_kernels reports (each name once, in launch order)
+ * "k_tgsw_dfa_v4(weights)" for the last bit (it reads the final weights), "k_tgsw_dfa_v4" for the
+ * bits in between and "k_tgsw_dfa_v4(extract)" for bit 0 (it extracts the start state's result);
+ * len = 1 is the single launch "k_tgsw_dfa_v4(weights+extract)"; then the key switch's own name. */
+typedef struct TfheAmdDfa TfheAmdDfa;
+int tfhe_amd_dfa_create(TfheAmdContext *ctx, int n_states, int start, const int32_t *next, int max_len,
+                        TfheAmdDfa **out);
+int tfhe_amd_dfa_destroy(TfheAmdDfa *dfa);
+int tfhe_amd_dfa_info(const TfheAmdDfa *dfa, int *n_states, int *start, int *max_len, int *device);
+int tfhe_amd_dfa_live(const TfheAmdDfa *dfa, int step, int32_t *states);
+int tfhe_amd_dfa_run_woks_dev(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                              const int32_t *sel, int n_fin, int fin_rows, const int32_t *fin,
+                              const int32_t *fin_index, int n_out, int32_t *u_a, int32_t *u_b, void *stream);
+int tfhe_amd_dfa_run_dev(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                         const int32_t *sel, int n_fin, int fin_rows, const int32_t *fin,
+                         const int32_t *fin_index, int n_out, int32_t *res_a, int32_t *res_b, void *stream);
+int tfhe_amd_dfa_run_woks_host(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                               const int32_t *sel, int n_fin, int fin_rows, const int32_t *fin,
+                               const int32_t *fin_index, int n_out, int32_t *u_a, int32_t *u_b);
+int tfhe_amd_dfa_run_host(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                          const int32_t *sel, int n_fin, int fin_rows, const int32_t *fin,
+                          const int32_t *fin_index, int n_out, int32_t *res_a, int32_t *res_b);
+
+/* Builders (host only, no GPU): they fill next [n_states][2] and *start and return the number of
+ * states, or TFHE_AMD_E_ARG for a null pointer or a parameter outside its range.
+ * tfhe_amd_dfa_build_compare: x against y over the word x_{d-1}, y_{d-1}, ..., x_0, y_0 (most
+ *   significant pair first, any d: len = 2 d): 5 states, next [5][2]; cls [5] (may be NULL) gets the
+ *   class of each state, after a whole number of pairs x < y, x = y or x > y, or between the two
+ *   bits of a pair.
+ * tfhe_amd_dfa_build_contains: the Knuth-Morris-Pratt automaton of the pattern of m bits
+ *   (pattern[0] is read first), 1 <= m <= 63: m + 1 states, next [m + 1][2]; state k = the longest
+ *   prefix of the pattern that ends the word read so far, state m absorbing: the word contains the
+ *   pattern.
+ * tfhe_amd_dfa_build_at_least: a saturating count of the ones up to t, 1 <= t <= 63: t + 1 states,
+ *   next [t + 1][2], state t absorbing: at least t bits are set.
+ * tfhe_amd_dfa_fin_fill: fin [n_states][1024] (one table at fin_rows = 1) with values
+ *   [n_states][n_out] at the coefficients 0 .. n_out - 1 of each state and zeros elsewhere,
+ *   1 <= n_out <= 16; returns TFHE_AMD_OK.
+ * tfhe_amd_dfa_simulate: the state after the plain word bits [len] (bit 0 first, len >= 0), or
+ *   TFHE_AMD_E_ARG for a bit outside {0, 1}, a transition outside [0, n_states) and bad shapes. */
+enum { TFHE_AMD_DFA_LT = 0, TFHE_AMD_DFA_EQ = 1, TFHE_AMD_DFA_GT = 2, TFHE_AMD_DFA_MID = 3 };
+int tfhe_amd_dfa_build_compare(int32_t *next, int *start, int32_t *cls);
+int tfhe_amd_dfa_build_contains(int m, const int32_t *pattern, int32_t *next, int *start);
+int tfhe_amd_dfa_build_at_least(int t, int32_t *next, int *start);
+int tfhe_amd_dfa_fin_fill(int n_states, int n_out, const int32_t *values, int32_t *fin);
+int tfhe_amd_dfa_simulate(int n_states, int start, const int32_t *next, int len, const int32_t *bits);
+
 /* ---- Packing key switch: computed LWE samples gathered into TLWE ciphertexts.
  * The public functional key switch with f = identity onto coefficient positions: P <= 1024 samples
  * (a_p, b_p) under the n = 500 LWE key become ONE TLWE ciphertext under the keyset's TLWE key whose
