@@ -863,6 +863,33 @@ class Context:
                                            ptr(cb_a), ptr(cb_b), ptr(cc_a), ptr(cc_b), stream),
                "gate_batch_dev")
 
+    def woks_dev(self, mu, x_a, x_b, u_a, u_b, stream=None):
+        """tfhe_amd_bootstrap_woks_batch_dev on torch tensors: x (n = 500) -> the extracted samples
+        u_a [B][1024], u_b [B]"""
+        B = x_a.shape[0]
+        for name, t, shape in (("x_a", x_a, (B, n_lwe)), ("x_b", x_b, (B,)), ("u_a", u_a, (B, N)), ("u_b", u_b, (B,))):
+            self._dev_check(t, shape, name)
+        _check(lib.tfhe_amd_bootstrap_woks_batch_dev(self.h, B, int(mu), x_a.data_ptr(), x_b.data_ptr(), u_a.data_ptr(),
+                                                     u_b.data_ptr(), stream), "bootstrap_woks_batch_dev")
+
+    def bootstrap_dev(self, mu, x_a, x_b, res_a, res_b, stream=None):
+        """tfhe_amd_bootstrap_batch_dev on torch tensors: woKS + key switch, res_a [B][500], res_b [B]"""
+        B = x_a.shape[0]
+        for name, t, shape in (("x_a", x_a, (B, n_lwe)), ("x_b", x_b, (B,)), ("res_a", res_a, (B, n_lwe)),
+                               ("res_b", res_b, (B,))):
+            self._dev_check(t, shape, name)
+        _check(lib.tfhe_amd_bootstrap_batch_dev(self.h, B, int(mu), x_a.data_ptr(), x_b.data_ptr(), res_a.data_ptr(),
+                                                res_b.data_ptr(), stream), "bootstrap_batch_dev")
+
+    def keyswitch_dev(self, u_a, u_b, res_a, res_b, stream=None):
+        """tfhe_amd_keyswitch_batch_dev on torch tensors: u_a [B][1024], u_b [B] -> res_a [B][500], res_b [B]"""
+        B = u_a.shape[0]
+        for name, t, shape in (("u_a", u_a, (B, N)), ("u_b", u_b, (B,)), ("res_a", res_a, (B, n_lwe)),
+                               ("res_b", res_b, (B,))):
+            self._dev_check(t, shape, name)
+        _check(lib.tfhe_amd_keyswitch_batch_dev(self.h, B, u_a.data_ptr(), u_b.data_ptr(), res_a.data_ptr(),
+                                                res_b.data_ptr(), stream), "keyswitch_batch_dev")
+
     # ---- programmable bootstrapping (tfhe_amd_bootstrap_lut_*): tv = test vectors [n_lut][1024] (or
     # one [1024]), lut_index [B] picks each ciphertext's table (None: table 0); the blind-rotation
     # input is (0, c) + sa X + sb Y
@@ -1759,8 +1786,9 @@ class Circuit:
         (list of wires) -> {wire: bit array}.  Convenience for tests and the bench."""
         import torch
         n_w = self.info()["wires"]
-        wa = torch.zeros((n_w, B, n_lwe), dtype=torch.int32, device="cuda")
-        wb = torch.zeros((n_w, B), dtype=torch.int32, device="cuda")
+        # every wire the run does not write stays this word (0xA5A5A5A5), not a plausible 0
+        wa = torch.full((n_w, B, n_lwe), -0x5A5A5A5B, dtype=torch.int32, device="cuda")
+        wb = torch.full((n_w, B), -0x5A5A5A5B, dtype=torch.int32, device="cuda")
         for w, bits in inputs.items():
             a, b = keyset.encrypt(np.asarray(bits), rng)
             wa[w] = torch.from_numpy(a).cuda()

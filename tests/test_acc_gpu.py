@@ -9,6 +9,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import dev_arena as DA
 import acc_oracle as AO
 import guard_cases as G
 import lut_oracle as LO
@@ -40,8 +41,9 @@ def _dev(x):
 
 
 def _zeros(shape):
+    """an output tensor: every word the constant poison of tests/dev_arena.py, not a plausible 0"""
     import torch
-    t = torch.zeros(tuple(shape), dtype=torch.int32, device="cuda")
+    t = DA.poisoned(shape)
     torch.cuda.synchronize()
     return t
 

@@ -12,6 +12,7 @@ import time
 import numpy as np
 import pytest
 
+import dev_arena as DA
 import dag_fuzz as DF
 import dag_oracle as DO
 import tfhe_amd as T
@@ -54,8 +55,8 @@ def _shape(profile):
 def _run(ctx, C, enc, B, n_w=None):
     import torch
     n_w = C.info()["wires"] if n_w is None else n_w
-    wa = torch.zeros((n_w, B, n_lwe), dtype=torch.int32, device="cuda")
-    wb = torch.zeros((n_w, B), dtype=torch.int32, device="cuda")
+    wa = DA.poisoned((n_w, B, n_lwe))      # every wire the run does not write stays poison
+    wb = DA.poisoned((n_w, B))
     for w, (a, b) in enc.items():
         wa[w] = torch.from_numpy(a).cuda()
         wb[w] = torch.from_numpy(b).cuda()

@@ -12,6 +12,7 @@ import time
 import numpy as np
 import pytest
 
+import dev_arena as DA
 import acc_oracle as AO
 import dag_oracle as DO
 import guard_cases as G
@@ -57,12 +58,14 @@ def _inputs(seed, ins, B):
     return {w: (_rand32(rng, (B, n_lwe)), _rand32(rng, B)) for w in ins}
 
 
-def _wires(C, enc, B, n_w=None):
-    """the wire arrays with the inputs filled, complete before a context's own stream may touch them"""
+def _wires(C, enc, B, n_w=None, zeros=False):
+    """the wire arrays with the inputs filled, complete before a context's own stream may touch them;
+    zeros: the buffer of a call that must refuse (the test asserts that no wire was written)"""
     import torch
     n_w = C.info()["wires"] if n_w is None else n_w
-    wa = torch.zeros((n_w, B, n_lwe), dtype=torch.int32, device="cuda")
-    wb = torch.zeros((n_w, B), dtype=torch.int32, device="cuda")
+    alloc = (lambda shape: torch.zeros(shape, dtype=torch.int32, device="cuda")) if zeros else DA.poisoned
+    wa = alloc((n_w, B, n_lwe))            # every wire a run does not write stays poison
+    wb = alloc((n_w, B))
     for w, (a, b) in enc.items():
         wa[w] = torch.from_numpy(np.ascontiguousarray(a)).cuda()
         wb[w] = torch.from_numpy(np.ascontiguousarray(b)).cuda()
@@ -341,7 +344,7 @@ def test_the_run_forms_without_a_pack_key_refuse_a_select_node(ctx, okey, keyset
     assert np.array_equal(ha0, ha1) and np.array_equal(hb0, hb1) and kern0 == kern1 and len(kern0) == 3
     _check_wires(C, DO.eval_circuit(C, okey, enc, B), ha1, hb1, "select-free circuit through run_pk_dev")
     s = C.select([g, ins[2]], ins[0])
-    wa, wb = _wires(C, enc, B)
+    wa, wb = _wires(C, enc, B, zeros=True)
     lib = T.lib
     assert lib.tfhe_amd_circuit_run_dev(ctx.h, C.h, B, wa.data_ptr(), wb.data_ptr(), None) == E_ARG
     assert ctx.last_kernels() == []

@@ -17,6 +17,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import dev_arena as DA
 import matvec
 import tfhe_amd as T
 
@@ -259,8 +260,8 @@ def test_circuits_every_wire_torus32_vs_oracle(ctx, okey, keyset, rng):
     for name, C, bits, B in _circuits_for_torus32():
         n_w = C.info()["wires"]
         enc = {w: keyset.encrypt(v, rng) for w, v in bits.items()}
-        wa = torch.zeros((n_w, B, n), dtype=torch.int32, device="cuda")
-        wb = torch.zeros((n_w, B), dtype=torch.int32, device="cuda")
+        wa = DA.poisoned((n_w, B, n))      # every wire the run does not write stays poison
+        wb = DA.poisoned((n_w, B))
         for w, (ea, eb) in enc.items():
             wa[w] = torch.from_numpy(ea).cuda()
             wb[w] = torch.from_numpy(eb).cuda()
@@ -292,8 +293,8 @@ def test_config4_mul_16x16_batch256_wires_torus32_sampled(ctx, okey, keyset, rng
     bits = {**_bits(a, x, nb), **_bits(b, y, nb)}
     n_w = C.info()["wires"]
     enc = {w: keyset.encrypt(v, rng) for w, v in bits.items()}
-    wa = torch.zeros((n_w, B, n), dtype=torch.int32, device="cuda")
-    wb = torch.zeros((n_w, B), dtype=torch.int32, device="cuda")
+    wa = DA.poisoned((n_w, B, n))      # every wire the run does not write stays poison
+    wb = DA.poisoned((n_w, B))
     for w, (ea, eb) in enc.items():
         wa[w] = torch.from_numpy(ea).cuda()
         wb[w] = torch.from_numpy(eb).cuda()
@@ -320,8 +321,8 @@ def test_circuit_rows_torus32_vs_oracle(ctx, okey, keyset, rng):
     B = 24
     bits = [rng.integers(0, 2, B) for _ in range(3)]
     n_w = C.info()["wires"]
-    wa = torch.zeros((n_w, B, n), dtype=torch.int32, device="cuda")
-    wb = torch.zeros((n_w, B), dtype=torch.int32, device="cuda")
+    wa = DA.poisoned((n_w, B, n))      # every wire the run does not write stays poison
+    wb = DA.poisoned((n_w, B))
     enc = [keyset.encrypt(v, rng) for v in bits]
     for w, (ea, eb) in zip((x, y, z), enc):
         wa[w] = torch.from_numpy(ea).cuda()

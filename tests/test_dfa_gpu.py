@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import dev_arena as DA
 import dfa_oracle as DO
 import tfhe_amd as T
 import tgsw_oracle as TO
@@ -38,8 +39,9 @@ def _dev(x):
 
 
 def _zeros(shape):
+    """an output tensor: every word the constant poison of tests/dev_arena.py, not a plausible 0"""
     import torch
-    t = torch.zeros(tuple(shape), dtype=torch.int32, device="cuda")
+    t = DA.poisoned(shape)
     torch.cuda.synchronize()
     return t
 

@@ -5,6 +5,7 @@ guard's exact recompute, and the circuits word for word and decoded."""
 import numpy as np
 import pytest
 
+import dev_arena as DA
 import fa_oracle as FO
 import many_lut_oracle as MO
 import tfhe_amd as T
@@ -73,8 +74,8 @@ def test_batch_decoded(ctx, okey, keyset, enc_sum, enc_carry):
         s, co = FO.cell_truth(m)
         assert np.array_equal(FO.decode(keyset, enc_sum, (got[0][0], got[1][0])), s)
         assert np.array_equal(FO.decode(keyset, enc_carry, (got[0][1], got[1][1])), co)
-        r_a = torch.zeros((2, 8, n_lwe), dtype=torch.int32, device="cuda")
-        r_b = torch.zeros((2, 8), dtype=torch.int32, device="cuda")
+        r_a = DA.poisoned((2, 8, n_lwe))
+        r_b = DA.poisoned((2, 8))
         ctx.full_add_dev(enc_sum, enc_carry, r_a, r_b, _dev(a), _dev(b), None if third is None else _dev(third))
         ctx.sync()
         assert _same((r_a.cpu().numpy(), r_b.cpu().numpy()), want)
@@ -104,8 +105,8 @@ def test_batch_random_words_and_rotation_edges(ctx, okey):
         assert _same(ctx.full_add_host(enc_sum, enc_carry, a, b, c), want)
         for alias in (0, 1, 2):   # the result's first block is the storage of a, b or c
             ins = [_dev(a), _dev(b), _dev(c)]
-            r_a = torch.zeros((2, B, n_lwe), dtype=torch.int32, device="cuda")
-            r_b = torch.zeros((2, B), dtype=torch.int32, device="cuda")
+            r_a = DA.poisoned((2, B, n_lwe))
+            r_b = DA.poisoned((2, B))
             r_a[0].copy_(ins[alias][0])
             r_b[0].copy_(ins[alias][1])
             ins[alias] = (r_a[0], r_b[0])
@@ -198,8 +199,8 @@ def test_batch_argument_errors(ctx):
 def _run(ctx, C, enc, B):
     import torch
     n_w = C.info()["wires"]
-    wa = torch.zeros((n_w, B, n_lwe), dtype=torch.int32, device="cuda")
-    wb = torch.zeros((n_w, B), dtype=torch.int32, device="cuda")
+    wa = DA.poisoned((n_w, B, n_lwe))      # every wire the run does not write stays poison
+    wb = DA.poisoned((n_w, B))
     for w, (a, b) in enc.items():
         wa[w] = torch.from_numpy(a).cuda()
         wb[w] = torch.from_numpy(b).cuda()

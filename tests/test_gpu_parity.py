@@ -221,12 +221,14 @@ def test_empty_batch_is_a_no_op(ctx, keyset, rng):
     assert np.array_equal(keyset.decrypt(r_a, r_b), 1 - x)
 
 
-@pytest.mark.parametrize("B", [1, 12, 13, 96, 255, 256, 257, 400, 768, 769, 1025])
+@pytest.mark.parametrize("B", [1, 12, 13, 96, 255, 256, 257, 400, 768, 769, 1025, 1792, 1793])
 def test_keyswitch_paths_bit_exact(ctx, okey, rng, B):
     """Each key-switch path at and around its threshold: small batch <= 12 (per-key-index
     workgroups, atomic partials), above it the int8 MFMA key switch (ks-v5; 256 ciphertexts per
-    workgroup: ragged last tile at 13 / 255 / 257 / 400 / 769 / 1025; key-index split 8 up to
-    256, 4 up to 512, 2 up to 1024, none above)."""
+    workgroup: ragged last tile at 13 / 255 / 257 / 400 / 769 / 1025 / 1793; key-index split
+    (ks5_split, constants that do not depend on the CU count) 8 up to 256, 4 from 257 to 768, 2 from
+    769 to 1792, none from 1793 on: 1793 is the unsplit kernel, the only one that stores instead of
+    adding, with 7 full tiles and one row)."""
     u_a = rng.integers(-2**31, 2**31, (B, N), dtype=np.int64).astype(np.int32)
     u_b = rng.integers(-2**31, 2**31, B, dtype=np.int64).astype(np.int32)
     k_a, k_b = ctx.keyswitch_host(u_a, u_b)

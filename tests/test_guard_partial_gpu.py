@@ -17,6 +17,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
+import dev_arena as DA
 import circuit_oracle
 import guard_cases as G
 import lut_oracle as LO
@@ -279,8 +280,8 @@ def test_circuit_level_slots(hctx, hkey, pool, P):
 
     def run(C, inputs):
         n_w = C.info()["wires"]
-        wa = torch.zeros((n_w, B, T.n_lwe), dtype=torch.int32, device="cuda")
-        wb = torch.zeros((n_w, B), dtype=torch.int32, device="cuda")
+        wa = DA.poisoned((n_w, B, T.n_lwe))      # every wire the run does not write stays poison
+        wb = DA.poisoned((n_w, B))
         for w, (e_a, e_b) in inputs.items():
             wa[w] = torch.from_numpy(e_a).cuda()
             wb[w] = torch.from_numpy(e_b).cuda()

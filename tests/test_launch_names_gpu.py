@@ -5,6 +5,7 @@ the half seam and of the pair seam."""
 import numpy as np
 import pytest
 
+import dev_arena as DA
 import tfhe_amd as T
 
 pytestmark = pytest.mark.gpu
@@ -93,8 +94,8 @@ def test_constant_circuit_level_takes_the_constant_rows_kernels(ctx, okey, keyse
     B = 5
     x, y = rng.integers(0, 2, B), rng.integers(0, 2, B)
     enc = {a: keyset.encrypt(x, rng), b: keyset.encrypt(y, rng)}
-    wa = torch.zeros((C.info()["wires"], B, T.n_lwe), dtype=torch.int32, device="cuda")
-    wb = torch.zeros((C.info()["wires"], B), dtype=torch.int32, device="cuda")
+    wa = DA.poisoned((C.info()["wires"], B, T.n_lwe))
+    wb = DA.poisoned((C.info()["wires"], B))
     for w, (e_a, e_b) in enc.items():
         wa[w] = torch.from_numpy(e_a).cuda()
         wb[w] = torch.from_numpy(e_b).cuda()

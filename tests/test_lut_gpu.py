@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+import dev_arena as DA
 import lut_oracle as LO
 import tfhe_amd as T
 
@@ -79,8 +80,8 @@ def test_random_tables_rotation_edges_host_and_dev(ctx, okey):
     assert _same(ctx.lut_bootstrap_host(tvs, x_a, x_b, idx), want_r)
 
     d = {k: torch.from_numpy(v).cuda() for k, v in (("tv", tvs), ("idx", idx), ("x_a", x_a), ("x_b", x_b))}
-    u_a = torch.zeros((B, N), dtype=torch.int32, device="cuda")
-    u_b = torch.zeros(B, dtype=torch.int32, device="cuda")
+    u_a = DA.poisoned((B, N))
+    u_b = DA.poisoned(B)
     ctx.lut_woks_dev(d["tv"], u_a, u_b, d["x_a"], d["x_b"], d["idx"])
     ctx.sync()
     assert _same((u_a.cpu().numpy(), u_b.cpu().numpy()), want_u)
@@ -100,12 +101,12 @@ def test_device_index_is_clamped(ctx, okey):
     idx = np.array([0, 1, -1, 2, -2**31, 2**31 - 1, 1, 0], np.int32)
     want = LO.woks_batch(okey, tvs, x_a, x_b, np.clip(idx, 0, 1))
     d = [torch.from_numpy(v).cuda() for v in (tvs, x_a, x_b, idx)]
-    u_a = torch.zeros((8, N), dtype=torch.int32, device="cuda")
-    u_b = torch.zeros(8, dtype=torch.int32, device="cuda")
+    u_a = DA.poisoned((8, N))
+    u_b = DA.poisoned(8)
     for threshold in (0.125, 0.0):
         try:
             T.set_guard_threshold(threshold)
-            u_a.zero_()
+            u_a.fill_(DA.POISON_I32)
             ctx.lut_woks_dev(d[0], u_a, u_b, d[1], d[2], d[3])
             ctx.sync()
         finally:
@@ -296,8 +297,8 @@ def _run_adder(ctx, case, B):
     import torch
     C, ins, outs, digits, bits, enc, W = case
     n_w = C.info()["wires"]
-    wa = torch.zeros((n_w, B, n_lwe), dtype=torch.int32, device="cuda")
-    wb = torch.zeros((n_w, B), dtype=torch.int32, device="cuda")
+    wa = DA.poisoned((n_w, B, n_lwe))      # every wire the run does not write stays poison
+    wb = DA.poisoned((n_w, B))
     for w, (a, b) in zip(ins, enc):
         wa[w] = torch.from_numpy(a).cuda()
         wb[w] = torch.from_numpy(b).cuda()

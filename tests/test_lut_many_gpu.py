@@ -9,6 +9,7 @@ import sys
 import numpy as np
 import pytest
 
+import dev_arena as DA
 import lut_oracle as LO
 import many_lut_oracle as MO
 import tfhe_amd as T
@@ -97,14 +98,14 @@ def test_random_tables_rotation_edges_host_and_dev(ctx, okey, theta, n_out):
     assert _same(ctx.lut_many_bootstrap_host(tvs, theta, n_out, x_a, x_b, idx), want_r)
 
     d = {k: torch.from_numpy(v).cuda() for k, v in (("tv", tvs), ("idx", idx), ("x_a", x_a), ("x_b", x_b))}
-    u_a = torch.zeros((n_out, B, N), dtype=torch.int32, device="cuda")
-    u_b = torch.zeros((n_out, B), dtype=torch.int32, device="cuda")
+    u_a = DA.poisoned((n_out, B, N))
+    u_b = DA.poisoned((n_out, B))
     ctx.lut_many_woks_dev(d["tv"], theta, n_out, u_a, u_b, d["x_a"], d["x_b"], d["idx"])
     ctx.sync()
     assert _same((u_a.cpu().numpy(), u_b.cpu().numpy()), want_u)
     # the key-switched result over the inputs: X is the first block of the result's storage
-    r_a = torch.zeros((n_out, B, n_lwe), dtype=torch.int32, device="cuda")
-    r_b = torch.zeros((n_out, B), dtype=torch.int32, device="cuda")
+    r_a = DA.poisoned((n_out, B, n_lwe))
+    r_b = DA.poisoned((n_out, B))
     r_a[0].copy_(d["x_a"])
     r_b[0].copy_(d["x_b"])
     ctx.lut_many_bootstrap_dev(d["tv"], theta, n_out, r_a, r_b, r_a[0], r_b[0], d["idx"])
@@ -260,8 +261,8 @@ def _run_adder(ctx, case, B):
     import torch
     C, ins, outs, digits, bits, enc, W = case
     n_w = C.info()["wires"]
-    wa = torch.zeros((n_w, B, n_lwe), dtype=torch.int32, device="cuda")
-    wb = torch.zeros((n_w, B), dtype=torch.int32, device="cuda")
+    wa = DA.poisoned((n_w, B, n_lwe))      # every wire the run does not write stays poison
+    wb = DA.poisoned((n_w, B))
     for w, (a, b) in zip(ins, enc):
         wa[w] = torch.from_numpy(a).cuda()
         wb[w] = torch.from_numpy(b).cuda()

@@ -9,6 +9,7 @@ and the int8-MFMA key switch, the kernels of the headline batch); every copy mus
 import numpy as np
 import pytest
 
+import dev_arena as DA
 import ref_fixture as RF
 import tfhe_amd as T
 
@@ -34,8 +35,9 @@ def _host(t):
 
 
 def _zeros(shape):
-    torch = _torch()
-    return torch.zeros(shape, dtype=torch.int32, device="cuda")
+    """an output tensor: every word the constant poison of tests/dev_arena.py, not a plausible 0"""
+    _torch()
+    return DA.poisoned(shape)
 
 
 @pytest.fixture(scope="module", autouse=True)
