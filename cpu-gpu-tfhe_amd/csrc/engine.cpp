@@ -721,6 +721,9 @@ extern "C" int tfhe_amd_keyswitch_batch_dev(TfheAmdContext *c, int B, const int3
     if (!c || B < 0 || !c->key.ksk) return TFHE_AMD_E_ARG;
     if (B == 0) return TFHE_AMD_OK;
     if (!u_a || !u_b || !res_a || !res_b) return TFHE_AMD_E_ARG;
+    // k_keyswitch_v4 / k_keyswitch_v5 read u_a as uint4: the one caller pointer with an alignment
+    // rule (include/tfhe_amd.h); every other entry point hands them the library's own scratch
+    if (reinterpret_cast<uintptr_t>(u_a) % 16) return TFHE_AMD_E_ARG;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     EntryFrame frame(c, 0);
     if (frame.rc) return frame.rc;

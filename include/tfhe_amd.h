@@ -126,7 +126,12 @@ int tfhe_amd_bootstrap_woks_batch_dev(TfheAmdContext *ctx, int B, int32_t mu,
 int tfhe_amd_bootstrap_batch_dev(TfheAmdContext *ctx, int B, int32_t mu,
                                  const int32_t *x_a, const int32_t *x_b,
                                  int32_t *res_a, int32_t *res_b, void *stream);
-/* lweKeySwitch over B samples u (N=1024) -> res (n=500) */
+/* lweKeySwitch over B samples u (N=1024) -> res (n=500).
+ * ALIGNMENT: u_a must be 16-byte aligned (the key-switch kernels read it 16 bytes at a time; a row is
+ * 4096 bytes, so every row then is); a u_a that is not is refused with TFHE_AMD_E_ARG on the host,
+ * before any launch.  This is the library's only alignment rule of its own: every other device
+ * pointer of every entry point needs 4-byte alignment only (every access to it is a 4-byte access).
+ * The host form below stages its input in the library's own scratch and takes any int32 pointer. */
 int tfhe_amd_keyswitch_batch_dev(TfheAmdContext *ctx, int B,
                                  const int32_t *u_a, const int32_t *u_b,
                                  int32_t *res_a, int32_t *res_b, void *stream);

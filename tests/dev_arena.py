@@ -6,7 +6,11 @@ An Arena is ONE int32 allocation that holds every tensor of one call under test:
     band | view | band | view | band | ...
 
   - every view starts at a multiple of ALIGN = 128 words (512 B), the alignment a fresh torch
-    allocation has, so no 16-byte vector load of a kernel behaves differently on a view;
+    allocation has, so no 16-byte vector load of a kernel behaves differently on a view; with
+    skew=True view k starts 1 + k mod 3 words behind that multiple instead (the words skipped belong
+    to the band in front of it), so its pointer is word-aligned only, as a caller's tightly packed
+    arrays are — except the views named in `aligned`, for the one pointer the library wants 16-byte
+    aligned (include/tfhe_amd.h: the u_a of tfhe_amd_keyswitch_batch_dev);
   - every view is followed by a band of at least BAND = 2048 poisoned words (two of the widest rows,
     1024 words, and more than the 512-thread key-switch block), the arena begins with such a band,
     and the alignment slack behind a view belongs to its band;
@@ -60,11 +64,19 @@ def _count(shape):
     return shape, n
 
 
-def words_for(shapes):
-    """arena words for views of these shapes, in this order"""
+SKEW_MAX = 3
+
+
+def skew_of(k):
+    """words view k of a skewed arena starts behind its 512-byte multiple: 1, 2, 3, 1, ..."""
+    return 1 + k % SKEW_MAX
+
+
+def words_for(shapes, skew=False):
+    """arena words for views of these shapes, in this order (skew: room for every view's offset)"""
     cur = BAND
     for s in shapes:
-        cur = _round_up(cur + _count(s)[1] + BAND, ALIGN)
+        cur = _round_up(cur + (SKEW_MAX if skew else 0) + _count(s)[1] + BAND, ALIGN)
     return cur
 
 
@@ -79,9 +91,11 @@ def _poison_words(kind, n, device):
 
 
 class Arena:
-    def __init__(self, device, poison, words, backing=None):
-        """words: the arena's size (words_for(shapes) of the views that will be asked for)"""
+    def __init__(self, device, poison, words, backing=None, skew=False, aligned=()):
+        """words: the arena's size (words_for(shapes, skew) of the views that will be asked for)"""
         self.device = torch.device(device)
+        self.skew = bool(skew)
+        self.aligned = frozenset(aligned)
         self.kind = poison
         self.words = int(words)
         if backing is None:
@@ -101,11 +115,11 @@ class Arena:
         self._sync()
 
     @classmethod
-    def of(cls, device, poison, outs=(), inps=(), backing=None):
+    def of(cls, device, poison, outs=(), inps=(), backing=None, skew=False, aligned=()):
         """the arena of one call: outs [(name, shape)], then inps [(name, host array)], in that order ->
         (arena, {name: view})"""
         shapes = [s for _, s in outs] + [np.asarray(h).shape for _, h in inps]
-        a = cls(device, poison, words_for(shapes), backing)
+        a = cls(device, poison, words_for(shapes, skew), backing, skew, aligned)
         v = {name: a.out(shape, name) for name, shape in outs}
         v.update(a.inp_many(inps))
         return a, v
@@ -117,11 +131,12 @@ class Arena:
 
     def _carve(self, shape, name):
         shape, n = _count(shape)
-        start, end = self.cur, self.cur + n
+        name = name if name is not None else f"view{len(self.views)}"
+        start = self.cur + (skew_of(len(self.views)) if self.skew and name not in self.aligned else 0)
+        end = start + n
         nxt = _round_up(end + BAND, ALIGN)
         if nxt > self.words:
             raise ValueError(f"arena of {self.words} words is too small for view {name!r} {shape}")
-        name = name if name is not None else f"view{len(self.views)}"
         assert name != START and all(name != v[0] for v in self.views), f"view name {name!r} taken"
         self.cur = nxt
         self.band_starts.append(end)

@@ -113,6 +113,63 @@ def test_planted_input_word_is_reported_and_aliased_exempts_only_the_named_input
         a.check(aliased=("res_a",))
 
 
+@pytest.mark.parametrize("poison", DA.POISONS)
+def test_skewed_views_are_word_aligned_only(poison):
+    """skew=True: view k starts 1 + k mod 3 words behind a 512-byte multiple, so no view is 16-byte
+    aligned and the offsets 1, 2, 3 take turns; the views named in `aligned` keep
+    the multiple; bands and views still tile the arena, every band is still at least BAND words, the
+    data is where the views say, and a planted word at either end of every band is reported"""
+    rng = np.random.default_rng(SEED)
+    inps = [("u_a", rng.integers(-2**31, 2**31, (5, 1024), dtype=np.int64).astype(np.int32)),
+            ("u_b", rng.integers(-2**31, 2**31, 5, dtype=np.int64).astype(np.int32)),
+            ("idx", np.arange(7, dtype=np.int32))]
+    a, v = DA.Arena.of("cpu", poison, OUTS, inps, skew=True, aligned=("u_a",))
+    assert a.words == DA.words_for([s for _, s in OUTS] + [h.shape for _, h in inps], skew=True)
+    assert [DA.skew_of(k) for k in range(5)] == [1, 2, 3, 1, 2]
+    want_skew = {"res_a": 1, "res_b": 2, "u_a": 0, "u_b": 1, "idx": 2}        # by position; u_a exempt
+    prev_end = 0
+    for name, start, end, is_input, _ in a.views:
+        assert start % DA.ALIGN == want_skew[name], (name, start)
+        assert (v[name].data_ptr() - a.buf.data_ptr()) == 4 * start and a.buf.data_ptr() % (4 * DA.ALIGN) == 0
+        assert v[name].data_ptr() % 4 == 0 and (v[name].data_ptr() % 16 == 0) == (name == "u_a"), name
+        assert v[name].is_contiguous() and start - prev_end >= DA.BAND, (name, start, prev_end)
+        prev_end = end
+    assert {s % DA.ALIGN for _, s, *_ in a.views} == {0, 1, 2}                # u_a took offset 3's place
+    assert a.cur - prev_end >= DA.BAND and a.cur <= a.words
+    bands = a.bands()
+    edges = sorted([(s, e) for _, s, e in bands] + [(s, e) for _, s, e, _, _ in a.views])
+    assert edges[0][0] == 0 and edges[-1][1] == a.cur
+    assert all(edges[i][1] == edges[i + 1][0] for i in range(len(edges) - 1))
+    assert all(e - s >= DA.BAND for _, s, e in bands)
+    for name, host in inps:
+        assert np.array_equal(v[name].numpy(), host), name
+    a.check()
+    for name, start, end in bands:
+        for w in (start, end - 1):
+            keep = int(a.buf[w])
+            a.buf[w] = 0
+            with pytest.raises(AssertionError, match=f"band after {name!r} damaged at offset {w - start} "):
+                a.check()
+            a.buf[w] = keep
+    flat = v["u_b"].view(-1)
+    flat[0] ^= 1
+    with pytest.raises(AssertionError, match="input 'u_b' changed at word 0:"):
+        a.check()
+    flat[0] ^= 1
+    a.check()
+
+
+def test_skew_is_off_by_default():
+    """the default layout is what it was: the same size and the same starts with and without the argument"""
+    shapes = [s for _, s in OUTS]
+    assert DA.words_for(shapes) == DA.words_for(shapes, skew=False) <= DA.words_for(shapes, skew=True)
+    assert DA.words_for([(DA.ALIGN - 2,)] * 4) < DA.words_for([(DA.ALIGN - 2,)] * 4, skew=True)    # the offsets need room
+    a, v = DA.Arena.of("cpu", "const", OUTS)
+    b, w = DA.Arena.of("cpu", "const", OUTS, skew=False)
+    assert [x[1:3] for x in a.views] == [x[1:3] for x in b.views] and all(x[1] % DA.ALIGN == 0 for x in a.views)
+    assert not a.skew and a.words == b.words
+
+
 def test_host_backing_and_shared_poison_function():
     """an arena over caller-owned memory (the pinned host buffers of the host entry points) lies in
     that memory; poisoned() is the constant poison"""

@@ -209,6 +209,43 @@ def test_device_api_rejects_bad_tensors(ctx):
             ctx.gate_dev("NAND", a, b, other, b, a, b)
 
 
+def test_keyswitch_dev_refuses_a_u_a_that_is_not_16_byte_aligned(ctx, okey, rng):
+    """include/tfhe_amd.h: the key-switch kernels read u_a 16 bytes at a time, so
+    tfhe_amd_keyswitch_batch_dev returns TFHE_AMD_E_ARG for a u_a at 4, 8 or 12 bytes past a 16-byte
+    boundary, on the host and before any launch: the poisoned outputs keep every word.  The same
+    rows at an aligned address, with u_b, res_a and res_b word-aligned only, give the oracle's words."""
+    torch = _torch()
+    import dev_arena as DA
+    B = 5
+    u_a = rng.integers(-2**31, 2**31, (B, N), dtype=np.int64).astype(np.int32)
+    u_b = rng.integers(-2**31, 2**31, B, dtype=np.int64).astype(np.int32)
+    raw = torch.zeros(B * N + 4, dtype=torch.int32, device="cuda")
+    assert raw.data_ptr() % 16 == 0
+    for off in (1, 2, 3):
+        view = raw[off:off + B * N].view(B, N)
+        view.copy_(torch.from_numpy(u_a))
+        arena, v = DA.Arena.of("cuda", "index", [("res_a", (B, n)), ("res_b", (B,))], [("u_b", u_b)], skew=True)
+        before = {k: v[k].clone() for k in ("res_a", "res_b")}
+        assert view.data_ptr() % 16 == 4 * off and view.is_contiguous()
+        rc = T.lib.tfhe_amd_keyswitch_batch_dev(ctx.h, B, view.data_ptr(), v["u_b"].data_ptr(), v["res_a"].data_ptr(),
+                                                v["res_b"].data_ptr(), None)
+        assert rc == -1, f"offset {off}: rc {rc}, not TFHE_AMD_E_ARG"
+        with pytest.raises(T.TfheAmdError):
+            ctx.keyswitch_dev(view, v["u_b"], v["res_a"], v["res_b"])
+        ctx.sync()
+        torch.cuda.synchronize()
+        assert all(torch.equal(v[k], before[k]) for k in before), f"offset {off}: a refused call wrote its outputs"
+        arena.check()
+    arena, v = DA.Arena.of("cuda", "const", [("res_a", (B, n)), ("res_b", (B,))], [("u_a", u_a), ("u_b", u_b)], skew=True,
+                           aligned=("u_a",))
+    assert v["u_a"].data_ptr() % 16 == 0 and all(v[k].data_ptr() % 16 for k in ("u_b", "res_a", "res_b"))
+    ctx.keyswitch_dev(v["u_a"], v["u_b"], v["res_a"], v["res_b"])
+    ctx.sync()
+    o_a, o_b = okey.keyswitch_batch(u_a, u_b)
+    assert np.array_equal(v["res_a"].cpu().numpy(), o_a) and np.array_equal(v["res_b"].cpu().numpy(), o_b)
+    arena.check()
+
+
 def test_empty_batch_is_a_no_op(ctx, keyset, rng):
     torch = _torch()
     e2 = torch.empty((0, n), dtype=torch.int32, device="cuda")
