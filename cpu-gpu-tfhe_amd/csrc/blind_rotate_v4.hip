@@ -276,6 +276,32 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4_rows(V4Arg
     }
 }
 
+// Mixed-key rows: slot = row r of one instance, grid-stride as above; each row is
+// computed (guard mode: recomputed when its flag says so) under the key of its own slot
+// (br_common.h ring_key) and reads its inputs in place from the caller's arrays (engine.h RingWires).
+template <int MINW, bool LUT = false>
+__global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4_rows_mk(V4Args g, RingKeys kr, long total,
+                                                                        const CircRow *__restrict__ rows,
+                                                                        RingWires wr, RingLut lt, int32_t mu,
+                                                                        int32_t *__restrict__ u_a,
+                                                                        int32_t *__restrict__ u_b, V4Guard gd) {
+    __shared__ V4Shared sh;
+    bool used = false;
+    for (long slot = blockIdx.x; slot < total; slot += gridDim.x) {
+        if (guard_skip(gd, (size_t)slot)) continue;
+        if (used) __syncthreads();
+        used = true;
+        const CircRow row = rows[slot];
+        RowTerms t;
+        row_terms(t, row, wr);
+        V4Args gk = g;
+        gk.bk = ring_key<uint32_t>(kr, slot);
+        const int32_t *tv = nullptr;
+        if constexpr (LUT) tv = lut_table(lt.tv, lt.lut_index, lt.n_lut, ring_entry(row.x, wr.n));
+        br_v4_body<LUT, false, false>(sh, gk, t, mu, u_a + (size_t)slot * kN, u_b + slot, tv);
+    }
+}
+
 __global__ __launch_bounds__(kV4Threads, 2) void k_blind_rotate_v4_debug(V4Args g, int iters, int32_t *__restrict__ acc,
                                                                       const int32_t *__restrict__ bara) {
     __shared__ V4Shared sh;
@@ -564,6 +590,28 @@ hipError_t launch_blind_rotate_v4_rows(const DeviceKey &key, int B, int nrows, c
                                                        mode_many(decltype(m)::value)>),
                                dim3((unsigned)grid), dim3(kV4Threads), 0, s, v4_args(key), B, total, rows, wa, wb, mu, u_a,
                                u_b, gd, (const int32_t *)nullptr);
+        });
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_blind_rotate_v4_rows_ring(const DeviceKey &key, const RingKeys &keys, int nrows, const CircRow *rows,
+                                            const RingWires &wires, const RingLut &lut, int32_t mu, int32_t *u_a,
+                                            int32_t *u_b, hipStream_t s, BrMode mode, const Guard *guard) {
+    if (nrows <= 0) return hipSuccess;
+    if (!key.tw2 || !key.tw4 || !keys.bk || !keys.row_key || keys.n_keys < 1 || !rows || wires.n < 1)
+        return hipErrorInvalidValue;
+    if (mode != BrMode::Const && mode != BrMode::Lut) return hipErrorInvalidValue;
+    if (mode == BrMode::Lut && (!lut.tv || lut.n_lut < 1)) return hipErrorInvalidValue;
+    const V4Guard gd = v4_guard(guard);
+    const long total = nrows;
+    const long grid = gd.flags && total > kGuardGrid ? kGuardGrid : total;
+    trace_kernel(KernelLabel("k_blind_rotate_v4_rows", mode, {"multi-key", gd.flags ? "guard" : nullptr}).s);
+    with_flag(mode == BrMode::Lut, [&](auto m) {
+        with_flag(gd.flags != nullptr, [&](auto f) {
+            hipLaunchKernelGGL((k_blind_rotate_v4_rows_mk<decltype(f)::value ? 1 : 2, decltype(m)::value>),
+                               dim3((unsigned)grid), dim3(kV4Threads), 0, s, v4_args(key), keys, total, rows, wires, lut,
+                               mu, u_a, u_b, gd);
         });
     });
     return hipGetLastError();

@@ -557,6 +557,29 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6_rows(V6Ar
                                                        l.tv, l.mo, TLWE ? acc + slot * 2 * kN : nullptr);
 }
 
+// Mixed-key rows: workgroup `base + blockIdx.x` is row r of one instance; it runs
+// the same body under the key of the row's own slot (br_common.h ring_key: clamped, wave-uniform),
+// through a local copy of the arguments whose bk is that key, and reads its inputs in place from
+// the caller's arrays (engine.h RingWires).  Modes Const and Lut.
+template <int WAVES, bool RREG, bool LUT = false>
+__global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6_rows_mk(V6Args g, RingKeys kr, long base,
+                                                                        const CircRow *__restrict__ rows,
+                                                                        RingWires wr, RingLut lt, int32_t mu,
+                                                                        int32_t *__restrict__ u_a,
+                                                                        int32_t *__restrict__ u_b) {
+    __shared__ V6Shared sh;
+    const long r = base + blockIdx.x;
+    const CircRow row = rows[r];
+    RowTerms t;
+    row_terms(t, row, wr);
+    V6Args gk = g;
+    gk.bk = ring_key<double2>(kr, r);
+    const int32_t *tv = nullptr;
+    if constexpr (LUT) tv = lut_table(lt.tv, lt.lut_index, lt.n_lut, ring_entry(row.x, wr.n));
+    br_v6_body<WAVES, RREG, 1, false, LUT, false, false>(sh.ct[0], sh.tw, gk, t, mu, u_a + (size_t)r * kN, u_b + r,
+                                                         (size_t)r, true, tv);
+}
+
 template <bool RREG>
 __global__ __launch_bounds__(kV6Threads, 2) void k_blind_rotate_v6_debug(V6Args g, int iters, int32_t *__restrict__ acc,
                                                                       const int32_t *__restrict__ bara) {
@@ -791,6 +814,31 @@ hipError_t launch_blind_rotate_v6_rows(const DeviceKey &key, int B, int nrows, c
                                                            mode_many(decltype(m)::value)>),
                                    dim3((unsigned)n), dim3(kV6Threads), 0, s, v6_args(key, n, guard), B, base, rows, wa, wb,
                                    mu, u_a, u_b, (const int32_t *)nullptr);
+            });
+        });
+    }
+    return hipGetLastError();
+}
+
+// the chunks, rotation and priority policy of launch_blind_rotate_v6_rows with B = 1; `key` gives the
+// twiddles and the device, the bootstrapping keys come from the ring's table
+hipError_t launch_blind_rotate_v6_rows_ring(const DeviceKey &key, const RingKeys &keys, int nrows, const CircRow *rows,
+                                            const RingWires &wires, const RingLut &lut, int32_t mu, int32_t *u_a,
+                                            int32_t *u_b, hipStream_t s, BrMode mode, const Guard *guard) {
+    if (nrows <= 0) return hipSuccess;
+    if (!key.tw6 || !keys.bk || !keys.row_key || keys.n_keys < 1 || !rows || wires.n < 1) return hipErrorInvalidValue;
+    if (mode != BrMode::Const && mode != BrMode::Lut) return hipErrorInvalidValue;
+    if (mode == BrMode::Lut && (!lut.tv || lut.n_lut < 1)) return hipErrorInvalidValue;
+    const long total = nrows, chunk = v6_chunk(key);
+    for (long base = 0; base < total; base += chunk) {
+        const long n = total - base < chunk ? total - base : chunk;
+        const bool rreg = v6_rreg(key, n);
+        trace_kernel(KernelLabel("k_blind_rotate_v6_rows", mode, {"multi-key", rreg ? "reg-rotation" : "lds-rotation"}).s);
+        with_flag(mode == BrMode::Lut, [&](auto m) {
+            with_flag(rreg, [&](auto f) {
+                hipLaunchKernelGGL((k_blind_rotate_v6_rows_mk<kV6Waves, decltype(f)::value, decltype(m)::value>),
+                                   dim3((unsigned)n), dim3(kV6Threads), 0, s, v6_args(key, n, guard), keys, base, rows,
+                                   wires, lut, mu, u_a, u_b);
             });
         });
     }

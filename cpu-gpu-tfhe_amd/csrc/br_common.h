@@ -51,6 +51,42 @@ __device__ __forceinline__ void row_terms(RowTerms &t, const CircRow &row, const
     wire(row.z, t.za, t.zb);
 }
 
+// Mixed-key rows (engine.h RingKeys / RingWires).  The entry index of a ring wire, clamped into [0, n).
+__device__ __forceinline__ int ring_entry(int w, int n) {
+    int i = w >> 2;
+    i = i < n ? i : n - 1;
+    return i > 0 ? i : 0;
+}
+__device__ __forceinline__ void row_terms(RowTerms &t, const CircRow &row, const RingWires &wr) {
+    auto wire = [&](int w, const int32_t *&pa, const int32_t *&pb) {
+        const int seg = w & 3;
+        // (selects, not an indexed array of the kernel argument: that would go through scratch)
+        const int32_t *a = seg == 0 ? wr.a0 : seg == 1 ? wr.a1 : seg == 2 ? wr.a2 : nullptr;
+        const int32_t *b = seg == 0 ? wr.b0 : seg == 1 ? wr.b1 : seg == 2 ? wr.b2 : nullptr;
+        if (w < 0 || !a || !b || wr.n <= 0) { pa = nullptr; pb = nullptr; return; }
+        const size_t i = (size_t)ring_entry(w, wr.n);
+        pa = a + i * kn;
+        pb = b + i;
+    };
+    t.c = row.c; t.sa = row.sa; t.sb = row.sb; t.sc = row.sc;
+    wire(row.x, t.xa, t.xb);
+    wire(row.y, t.ya, t.yb);
+    wire(row.z, t.za, t.zb);
+}
+// The key of row r: its slot from device memory, clamped into [0, n_keys) before any address is
+// formed, then the slot's pointer made wave-uniform half by half (fft_wave.h uni), so that what the
+// body builds from it (v6: the key's buffer resource) stays in scalar registers.
+template <class T>
+__device__ __forceinline__ const T *ring_key(const RingKeys &kr, long r) {
+    int k = kr.row_key[r];
+    k = k < kr.n_keys ? k : kr.n_keys - 1;
+    k = k > 0 ? k : 0;
+    const unsigned long long bits = (unsigned long long)reinterpret_cast<uintptr_t>(kr.bk[k]);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)bits);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(bits >> 32));
+    return reinterpret_cast<const T *>((uintptr_t)(((unsigned long long)hi << 32) | lo));
+}
+
 // The test vector and the extra outputs of one ciphertext.  Compile-time null / default for the
 // constant instantiations, which form no table address.
 struct LutArgs {

@@ -335,6 +335,40 @@ hipError_t launch_blind_rotate_rows_tlwe(const DeviceKey &key, int B, int nrows,
                                          const int32_t *wb, const int32_t *acc, int32_t *u_a, int32_t *u_b,
                                          hipStream_t s, const Guard *guard);
 
+// ---- mixed-key rows (keyring.cpp): one rows launch over ciphertexts of several cloud
+// keys.  Row r runs under key slot row_key[r], clamped by the kernel into [0, n_keys) before the slot's
+// key pointer is loaded from bk (bk_fft pointers for the v6 launch, bk_v2 pointers for the v4 one);
+// twiddles and CRT constants come from the DeviceKey the launcher is given.  One instance per row.
+struct RingKeys {
+    const void *const *bk;     // [n_keys] device table of per-slot key pointers
+    const int32_t *row_key;    // [nrows] device
+    int32_t n_keys;
+};
+// The rows' inputs stay in the caller's arrays: wire w of a ring row is entry w >> 2 (clamped into
+// [0, n)) of input array w & 3 (a0 / a1 / a2; 3 and a null array: absent), -1 absent as in CircRow.
+struct RingWires {
+    const int32_t *a0, *b0, *a1, *b1, *a2, *b2;
+    int32_t n;
+};
+// mode Lut: the row whose x wire is entry i takes table lut_index[i] (null: 0; clamped) of tv [n_lut][kN]
+struct RingLut {
+    const int32_t *tv = nullptr;
+    const int32_t *lut_index = nullptr;
+    int32_t n_lut = 0;
+};
+// The geometry, rotation and priority policy of launch_blind_rotate_v6_rows (modes Const and Lut);
+// trace name "k_blind_rotate_v6_rows(multi-key+...)".
+hipError_t launch_blind_rotate_v6_rows_ring(const DeviceKey &key, const RingKeys &keys, int nrows, const CircRow *rows,
+                                            const RingWires &wires, const RingLut &lut, int32_t mu, int32_t *u_a,
+                                            int32_t *u_b, hipStream_t s, BrMode mode, const Guard *guard = nullptr);
+// the exact kernel over the same rows, in guard mode (guard set) or alone
+hipError_t launch_blind_rotate_v4_rows_ring(const DeviceKey &key, const RingKeys &keys, int nrows, const CircRow *rows,
+                                            const RingWires &wires, const RingLut &lut, int32_t mu, int32_t *u_a,
+                                            int32_t *u_b, hipStream_t s, BrMode mode, const Guard *guard = nullptr);
+// bootstrap-free ring entries: res[e.out] = (0, e.c) + e.s W[e.in] over ring wires (in = -1: trivial)
+hipError_t launch_ring_linear(int nlin, const CircLin *lin, const RingWires &wires, int32_t *res_a, int32_t *res_b,
+                              hipStream_t s);
+
 // which key-switch kernel the larger batches take: 5 (int8 MFMA), or 4 with TFHE_AMD_KS5=0
 int ks_version();
 size_t ksk_v4_words();

@@ -669,6 +669,39 @@ hipError_t launch_circuit_linear(int B, int nlin, const CircLin *lin, int32_t *w
     return hipGetLastError();
 }
 
+// bootstrap-free entries of a mixed-key batch (engine.h RingWires): res[out] = (0, c) + s W[in]; one
+// thread per (entry, word); the wire's entry index and out are clamped into [0, n) before they index
+__global__ __launch_bounds__(256) void k_ring_linear(int nlin, const CircLin *__restrict__ lin, RingWires wr,
+                                                     int32_t *res_a, int32_t *res_b) {
+    const size_t total = (size_t)nlin * (kn + 1);
+    for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (size_t)gridDim.x * 256) {
+        const int w = (int)(t % (kn + 1));
+        const CircLin e = lin[t / (kn + 1)];
+        const int seg = e.in & 3;
+        const int32_t *a = seg == 0 ? wr.a0 : seg == 1 ? wr.a1 : seg == 2 ? wr.a2 : nullptr;
+        const int32_t *b = seg == 0 ? wr.b0 : seg == 1 ? wr.b1 : seg == 2 ? wr.b2 : nullptr;
+        const bool absent = e.in < 0 || !a || !b;
+        int i = e.in >> 2, o = e.out;
+        i = i < wr.n ? i : wr.n - 1;
+        i = i > 0 ? i : 0;
+        o = o < wr.n ? o : wr.n - 1;
+        o = o > 0 ? o : 0;
+        if (w < kn) res_a[(size_t)o * kn + w] = absent ? 0 : (int32_t)((uint32_t)e.s * (uint32_t)a[(size_t)i * kn + w]);
+        else res_b[o] = (int32_t)((uint32_t)e.c + (absent ? 0u : (uint32_t)e.s * (uint32_t)b[i]));
+    }
+}
+
+hipError_t launch_ring_linear(int nlin, const CircLin *lin, const RingWires &wires, int32_t *res_a, int32_t *res_b,
+                              hipStream_t s) {
+    if (nlin <= 0) return hipSuccess;
+    if (!lin || !res_a || !res_b || wires.n < 1) return hipErrorInvalidValue;
+    const size_t total = (size_t)nlin * (kn + 1);
+    const int blocks = (int)std::min<size_t>((total + 255) / 256, 65536);
+    trace_kernel("k_ring_linear");
+    hipLaunchKernelGGL(k_ring_linear, dim3(blocks), dim3(256), 0, s, nlin, lin, wires, res_a, res_b);
+    return hipGetLastError();
+}
+
 hipError_t launch_ksk_to_v4(const int32_t *d_ksk, int32_t *d_ksk4, hipStream_t s) {
     hipLaunchKernelGGL(k_ksk_to_v4, dim3(2048), dim3(256), 0, s, d_ksk, reinterpret_cast<uint4 *>(d_ksk4));
     return hipGetLastError();

@@ -1816,3 +1816,153 @@ def bits_of(x, nbits):
 
 def int_of(planes):
     return sum(np.asarray(p, dtype=np.int64) << i for i, p in enumerate(planes))
+
+
+# --------------------------------------------------------------------- mixed-key batches
+
+lib.tfhe_amd_keyring_create.argtypes = [_VPP, ctypes.c_int, _VPP]
+lib.tfhe_amd_keyring_destroy.argtypes = [_VP]
+lib.tfhe_amd_keyring_count.argtypes = [_VP]
+lib.tfhe_amd_keyring_device.argtypes = [_VP]
+lib.tfhe_amd_keyring_plan.argtypes = [ctypes.c_int, ctypes.c_int, _IP, _IP, _IP, _IP, _IP]
+lib.tfhe_amd_keyring_gate_batch_dev.argtypes = [_VP, ctypes.c_int, _IP, _IP] + [_VP] * 8 + [_VP]
+lib.tfhe_amd_keyring_gate_batch_host.argtypes = [_VP, ctypes.c_int, _IP, _IP] + [_I32P] * 8
+lib.tfhe_amd_keyring_bootstrap_lut_batch_dev.argtypes = [_VP, ctypes.c_int, _IP, ctypes.c_int] + [_VP] * 6 + [_VP]
+lib.tfhe_amd_keyring_bootstrap_lut_batch_host.argtypes = [_VP, ctypes.c_int, _IP, ctypes.c_int] + [_I32P] * 6
+
+
+def _ip(a):
+    return a.ctypes.data_as(_IP)
+
+
+class KeyRing:
+    """TfheAmdKeyRing: 1 .. 256 contexts of one GPU as key slots; its batch calls take ciphertexts of
+    any slot's key (key_of [B], host) in one blind-rotation launch chain.  The ring borrows the
+    contexts' keys and runs in contexts[0]'s frame (stream, scratch, guard_stats, last_kernels):
+    close it before them (it keeps them referenced until then)."""
+
+    def __init__(self, contexts):
+        self.contexts = list(contexts)
+        arr = (_VP * max(len(self.contexts), 1))(*[c.h for c in self.contexts])
+        h = _VP()
+        _check(lib.tfhe_amd_keyring_create(arr, len(self.contexts), ctypes.byref(h)), "tfhe_amd_keyring_create")
+        self.h = h.value
+        self.device = lib.tfhe_amd_keyring_device(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib.tfhe_amd_keyring_destroy(self.h)
+            self.h = None
+        self.contexts = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return lib.tfhe_amd_keyring_count(self.h)
+
+    @staticmethod
+    def _codes(gates):
+        if isinstance(gates, np.ndarray) and gates.dtype.kind in "iu":   # codes already (large batches)
+            return np.ascontiguousarray(gates, dtype=np.int32)
+        return np.array([GATES[x] if isinstance(x, str) else int(x) for x in gates], dtype=np.int32)
+
+    @staticmethod
+    def plan_of(n_keys, key_of, gates=None):
+        """tfhe_amd_keyring_plan -> (order [B], offsets [n_keys + 1], rows); needs no GPU"""
+        k = np.ascontiguousarray(key_of, dtype=np.int32); B = k.shape[0]
+        g = None if gates is None else KeyRing._codes(gates)
+        if g is not None and g.shape != (B,):
+            raise TfheAmdError(f"gates: need one gate kind per ciphertext ({B}), got {g.shape[0]}")
+        order = np.zeros(B, np.int32); offsets = np.zeros(max(int(n_keys), 0) + 1, np.int32); rows = ctypes.c_int()
+        _check(lib.tfhe_amd_keyring_plan(B, int(n_keys), _ip(k), None if g is None else _ip(g), _ip(order),
+                                         _ip(offsets), ctypes.byref(rows)), "tfhe_amd_keyring_plan")
+        return order, offsets, rows.value
+
+    def plan(self, key_of, gates=None):
+        return self.plan_of(len(self), key_of, gates)
+
+    def _keys(self, key_of, B):
+        k = np.ascontiguousarray(key_of, dtype=np.int32)
+        if k.shape != (B,):
+            raise TfheAmdError(f"key_of: need one key slot per ciphertext ({B}), got {k.shape}")
+        return k
+
+    def gate_host(self, gates, key_of, ca_a, ca_b, cb_a=None, cb_b=None, cc_a=None, cc_b=None):
+        """tfhe_amd_keyring_gate_batch_host: gate i of kind gates[i] under key slot key_of[i]"""
+        ca_a = i32(ca_a); B = ca_a.shape[0]
+        g = self._codes(gates)
+        if g.shape != (B,):
+            raise TfheAmdError(f"gates: need one gate kind per row ({B}), got {g.shape[0]}")
+        k = self._keys(key_of, B)
+        r_a = np.zeros((B, n_lwe), np.int32); r_b = np.zeros(B, np.int32)
+        opt = lambda x: _p(None if x is None else i32(x))
+        _check(lib.tfhe_amd_keyring_gate_batch_host(self.h, B, _ip(g), _ip(k), _p(r_a), _p(r_b), _p(ca_a), _p(i32(ca_b)),
+                                                    opt(cb_a), opt(cb_b), opt(cc_a), opt(cc_b)),
+               "keyring_gate_batch_host")
+        return r_a, r_b
+
+    def _dev_check(self, t, shape, name):
+        if t is None:
+            raise TfheAmdError(f"{name}: missing tensor")
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise TfheAmdError(f"{name}: need a contiguous int32 GPU tensor of shape {shape}, got "
+                               f"{tuple(t.shape)} {t.dtype} cuda={t.is_cuda} contiguous={t.is_contiguous()}")
+        if t.device.index is not None and t.device.index != self.device:
+            raise TfheAmdError(f"{name}: tensor is on cuda:{t.device.index}, the ring on cuda:{self.device}")
+
+    def gate_dev(self, gates, key_of, res_a, res_b, ca_a, ca_b, cb_a=None, cb_b=None, cc_a=None, cc_b=None,
+                 stream=None):
+        """tfhe_amd_keyring_gate_batch_dev on torch tensors (as Context.gate_dev); gates and key_of
+        are host sequences"""
+        B = ca_a.shape[0]
+        g = self._codes(gates)
+        if g.shape != (B,):
+            raise TfheAmdError(f"gates: need one gate kind per row ({B}), got {g.shape[0]}")
+        k = self._keys(key_of, B)
+        named = [("res_a", res_a, (B, n_lwe)), ("res_b", res_b, (B,)), ("ca_a", ca_a, (B, n_lwe)), ("ca_b", ca_b, (B,))]
+        if ((g != GATES["NOT"]) & (g != GATES["COPY"])).any():
+            named += [("cb_a", cb_a, (B, n_lwe)), ("cb_b", cb_b, (B,))]
+        if (g == GATES["MUX"]).any():
+            named += [("cc_a", cc_a, (B, n_lwe)), ("cc_b", cc_b, (B,))]
+        for name, t, shape in named:
+            self._dev_check(t, shape, name)
+        ptr = (lambda t: None if t is None else t.data_ptr())
+        _check(lib.tfhe_amd_keyring_gate_batch_dev(self.h, B, _ip(g), _ip(k), ptr(res_a), ptr(res_b), ptr(ca_a),
+                                                   ptr(ca_b), ptr(cb_a), ptr(cb_b), ptr(cc_a), ptr(cc_b), stream),
+               "keyring_gate_batch_dev")
+
+    def lut_bootstrap_host(self, tv, key_of, x_a, x_b, lut_index=None):
+        """tfhe_amd_keyring_bootstrap_lut_batch_host -> (r_a [B][500], r_b [B])"""
+        tv = i32(tv).reshape(-1, N)
+        x_a = i32(x_a); B = x_a.shape[0]
+        idx = None if lut_index is None else i32(lut_index)
+        if idx is not None and idx.shape != (B,):
+            raise TfheAmdError(f"lut_index: need one table index per ciphertext ({B}), got {idx.shape}")
+        k = self._keys(key_of, B)
+        r_a = np.zeros((B, n_lwe), np.int32); r_b = np.zeros(B, np.int32)
+        _check(lib.tfhe_amd_keyring_bootstrap_lut_batch_host(self.h, B, _ip(k), tv.shape[0], _p(tv), _p(idx), _p(r_a),
+                                                             _p(r_b), _p(x_a), _p(i32(x_b))),
+               "keyring_bootstrap_lut_batch_host")
+        return r_a, r_b
+
+    def lut_bootstrap_dev(self, tv, key_of, res_a, res_b, x_a, x_b, lut_index=None, stream=None):
+        """tfhe_amd_keyring_bootstrap_lut_batch_dev on torch tensors; a lut_index entry outside
+        [0, n_lut) is clamped by the kernel"""
+        B = x_a.shape[0]
+        if tv is None or tv.dim() != 2 or tv.shape[0] < 1:
+            raise TfheAmdError("tv: need a GPU tensor [n_lut][1024]")
+        k = self._keys(key_of, B)
+        named = [("tv", tv, (tv.shape[0], N)), ("res_a", res_a, (B, n_lwe)), ("res_b", res_b, (B,)),
+                 ("x_a", x_a, (B, n_lwe)), ("x_b", x_b, (B,))]
+        if lut_index is not None:
+            named.append(("lut_index", lut_index, (B,)))
+        for name, t, shape in named:
+            self._dev_check(t, shape, name)
+        _check(lib.tfhe_amd_keyring_bootstrap_lut_batch_dev(
+            self.h, B, _ip(k), tv.shape[0], tv.data_ptr(), None if lut_index is None else lut_index.data_ptr(),
+            res_a.data_ptr(), res_b.data_ptr(), x_a.data_ptr(), x_b.data_ptr(), stream),
+            "keyring_bootstrap_lut_batch_dev")

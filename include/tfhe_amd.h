@@ -939,6 +939,61 @@ int tfhe_amd_circuit_abs(TfheAmdCircuit *c, int nbits, const int *a, int *out);
 int tfhe_amd_circuit_divu(TfheAmdCircuit *c, int nbits, const int *a, const int *b, int *q, int *r);
 int tfhe_amd_circuit_div(TfheAmdCircuit *c, int nbits, const int *a, const int *b, int *q);
 
+/* ---- Key ring: mixed-key batches.  A context is one cloud key and every batch
+ * entry point above takes one context; a ring names 1 .. 256 contexts of ONE device as its slots
+ * 0 .. n_keys - 1, and its batch entry points take ciphertexts of any of those keys in one call:
+ * ciphertext b belongs to slot key_of[b], in any order, and all of them share one blind-rotation
+ * launch chain (each row under its own bootstrapping key) and one guard launch; the key switch runs
+ * once per slot that has ciphertexts in the call.  Results are, word for word, what each member's
+ * own entry points give on its ciphertexts.
+ * The ring BORROWS its members' device keys: it neither copies nor frees them, and it owns only a
+ * small device table of per-slot key pointers and its row tables.  LIFETIME: destroy the ring before
+ * any of its members.  The same context may sit in several slots.
+ * A ring call executes in member 0's frame: its stream when `stream` is NULL, its scratch, its guard
+ * counters and its launch trace, so tfhe_amd_guard_stats, tfhe_amd_last_kernels and tfhe_amd_sync
+ * on member 0 report ring calls.  Calls on one ring are serialised.
+ * Anything but 1 <= n_keys <= 256 contexts on one device, each with a bootstrapping and a
+ * key-switching key, is TFHE_AMD_E_ARG. */
+typedef struct TfheAmdKeyRing TfheAmdKeyRing;
+int tfhe_amd_keyring_create(TfheAmdContext *const *ctxs, int n_keys, TfheAmdKeyRing **out);
+int tfhe_amd_keyring_destroy(TfheAmdKeyRing *ring);
+int tfhe_amd_keyring_count(const TfheAmdKeyRing *ring);    /* slots, or TFHE_AMD_E_ARG */
+int tfhe_amd_keyring_device(const TfheAmdKeyRing *ring);   /* device index, or -1 */
+/* The order a ring call works in (pure host function): order [B] = the batch indices sorted by key
+ * slot, stable; offsets [n_keys + 1] = where each slot's group starts in `order`; *rows = the blind
+ * rotations of the batch (a MUX counts two, TFHE_GATE_NOT / TFHE_GATE_COPY none; gates == NULL: one
+ * per ciphertext, the LUT form).  Any output may be NULL.  TFHE_AMD_E_ARG for B < 0, n_keys outside
+ * [1, 256], a slot outside [0, n_keys) or a gate the ring's gate forms do not take. */
+int tfhe_amd_keyring_plan(int B, int n_keys, const int *key_of, const int *gates,
+                          int *order, int *offsets, int *rows);
+/* B gates of mixed kinds over mixed keys: gates [B] and key_of [B] are HOST arrays (as gates is in
+ * tfhe_amd_gate_batch_mixed_host); gate kinds TFHE_GATE_NAND .. TFHE_GATE_MUX as there, and the
+ * linear TFHE_GATE_NOT / TFHE_GATE_COPY of ca (no bootstrap, no key).  cb_* may be NULL when every
+ * gate is linear, cc_* when none is a MUX.  A bad slot or gate code is TFHE_AMD_E_ARG before anything
+ * is launched or written; B = 0 is TFHE_AMD_OK with no launch.  The inputs are read in place and
+ * res [0, B) is all that is written; res may alias an input array (entry for entry). */
+int tfhe_amd_keyring_gate_batch_dev(TfheAmdKeyRing *ring, int B, const int *gates, const int *key_of,
+                                    int32_t *res_a, int32_t *res_b,
+                                    const int32_t *ca_a, const int32_t *ca_b,
+                                    const int32_t *cb_a, const int32_t *cb_b,
+                                    const int32_t *cc_a, const int32_t *cc_b, void *stream);
+int tfhe_amd_keyring_gate_batch_host(TfheAmdKeyRing *ring, int B, const int *gates, const int *key_of,
+                                     int32_t *res_a, int32_t *res_b,
+                                     const int32_t *ca_a, const int32_t *ca_b,
+                                     const int32_t *cb_a, const int32_t *cb_b,
+                                     const int32_t *cc_a, const int32_t *cc_b);
+/* Programmable bootstrap + key switch of x over mixed keys (tfhe_amd_bootstrap_lut_batch_* with
+ * cst = 0, sa = 1, sb = 0): tv [n_lut][1024] and lut_index [B] (NULL: table 0; clamped by the kernel)
+ * are device arrays in the dev form and host arrays in the host form; key_of is a host array. */
+int tfhe_amd_keyring_bootstrap_lut_batch_dev(TfheAmdKeyRing *ring, int B, const int *key_of, int n_lut,
+                                             const int32_t *tv, const int32_t *lut_index,
+                                             int32_t *res_a, int32_t *res_b,
+                                             const int32_t *x_a, const int32_t *x_b, void *stream);
+int tfhe_amd_keyring_bootstrap_lut_batch_host(TfheAmdKeyRing *ring, int B, const int *key_of, int n_lut,
+                                              const int32_t *tv, const int32_t *lut_index,
+                                              int32_t *res_a, int32_t *res_b,
+                                              const int32_t *x_a, const int32_t *x_b);
+
 #ifdef __cplusplus
 }
 #endif
