@@ -437,7 +437,10 @@ __global__ __launch_bounds__(kV4Threads, 2) void k_tgsw_cmux_v4(V4Args g, TgswCm
 // Every index read from device memory is wave-uniform and checked before an address is formed: a
 // state or transition outside [0, Q) ends the workgroup, a selector outside [0, count) and a state
 // with next0 == next1 (whose product is exactly zero) give out = d0, fin_index is clamped.
-template <bool FIRST, bool LAST>
+// TW (transition weights): d_b gains w_b = w_val[st][b] at coefficient p = *w_pos of
+// its b polynomial, so the thread that owns word kN + p adds w1 - w0 to the difference and w0 to the
+// result; the state copies only when w0 == w1 too.  A p outside [0, kN) makes the step weightless.
+template <bool FIRST, bool LAST, bool TW>
 __global__ __launch_bounds__(kV4Threads, 2) void k_tgsw_dfa_v4(V4Args g, TgswDfaStep a) {
     __shared__ V4Shared sh;
     const int tid = threadIdx.x;
@@ -462,28 +465,40 @@ __global__ __launch_bounds__(kV4Threads, 2) void k_tgsw_dfa_v4(V4Args g, TgswDfa
     }
     const int32_t *d0 = base + (size_t)n0 * rows * kN, *d1 = base + (size_t)n1 * rows * kN;
     const int idx = tgsw_sel(a.sel + (size_t)q * a.sel_stride);
-    const bool live = n0 != n1 && idx >= 0 && idx < a.count;
+    uint32_t w0 = 0u, w1 = 0u;
+    int wj = -1;   // the word of the weighted coefficient, j = kN + p; -1: a weightless step
+    if constexpr (TW) {
+        const int p = tgsw_sel(a.w_pos);
+        if (p >= 0 && p < kN) {
+            wj = kN + p;
+            w0 = (uint32_t)tgsw_sel(a.w_val + 2 * st);
+            w1 = (uint32_t)tgsw_sel(a.w_val + 2 * st + 1);
+        }
+    }
+    const bool live = (n0 != n1 || w0 != w1) && idx >= 0 && idx < a.count;
     // word j of an operand, j < 2 kN; rows = 1: the mask is zero and the body is the one row
     auto word = [&](const int32_t *d, int j) -> uint32_t {
         if (rows == 1 && j < kN) return 0u;
         return (uint32_t)d[rows == 1 ? j - kN : j];
     };
+    // what the transition weight adds to word j: w on the one word kN + p, nothing elsewhere
+    auto weight = [&](int j, uint32_t w) -> uint32_t { return TW && j == wj ? w : 0u; };
     if (live) {
         for (int j = tid; j < 2 * kN; j += kV4Threads)
-            e_store(sh.E[j >> kLogN], j & (kN - 1), word(d1, j) - word(d0, j) + (1u << 11));
+            e_store(sh.E[j >> kLogN], j & (kN - 1), word(d1, j) - word(d0, j) + (1u << 11) + weight(j, w1 - w0));
         __syncthreads();
         cmux_v4<true>(sh, g, idx, 0, s, L);
     }
     if constexpr (!LAST) {
         int32_t *out = a.dst + ((size_t)q * a.Q + st) * 2 * kN;
         for (int j = tid; j < 2 * kN; j += kV4Threads)
-            out[j] = (int32_t)(word(d0, j) + (live ? sh.E[j >> kLogN][j & (kN - 1)] : 0u));
+            out[j] = (int32_t)(word(d0, j) + weight(j, w0) + (live ? sh.E[j >> kLogN][j & (kN - 1)] : 0u));
     } else {
         // each thread replaces the words it read: the sum as the periodic extension the extraction reads
         for (int j = tid; j < 2 * kN; j += kV4Threads) {
             uint32_t *E = sh.E[j >> kLogN];
             const int k = j & (kN - 1);
-            e_store(E, k, word(d0, j) + (live ? E[k] : 0u));
+            e_store(E, k, word(d0, j) + weight(j, w0) + (live ? E[k] : 0u));
         }
         __syncthreads();
         for (int f = 0; f < a.n_out; ++f) {   // extraction at index f: a_j = E_a[(f - j) mod 2N], b = acc_b[f]
@@ -683,15 +698,23 @@ hipError_t launch_tgsw_dfa_v4(const DeviceKey &key, const uint32_t *set, const T
         a.n_live > a.Q || (long)a.B * a.n_live > 0x7fffffffL)
         return hipErrorInvalidValue;
     if (first ? (!a.fin || a.n_fin < 1 || a.fin_rows < 1 || a.fin_rows > 2) : !a.src) return hipErrorInvalidValue;
-    if (last ? (a.n_live != 1 || !a.u_a || !a.u_b || a.n_out < 1 || a.n_out > 16 || a.u_stride < a.B)
+    const bool tw = a.w_val != nullptr;   // transition weights: both arrays or neither
+    if (tw != (a.w_pos != nullptr)) return hipErrorInvalidValue;
+    if (last ? (a.n_live != 1 || !a.u_a || !a.u_b || a.n_out < 1 || a.n_out > (tw ? 64 : 16) || a.u_stride < a.B)
              : (!a.dst || a.dst == a.src))
         return hipErrorInvalidValue;
-    trace_kernel(first ? (last ? "k_tgsw_dfa_v4(weights+extract)" : "k_tgsw_dfa_v4(weights)")
-                       : (last ? "k_tgsw_dfa_v4(extract)" : "k_tgsw_dfa_v4"));
+    if (tw)
+        trace_kernel(first ? (last ? "k_tgsw_dfa_v4(weights+tw+extract)" : "k_tgsw_dfa_v4(weights+tw)")
+                           : (last ? "k_tgsw_dfa_v4(tw+extract)" : "k_tgsw_dfa_v4(tw)"));
+    else
+        trace_kernel(first ? (last ? "k_tgsw_dfa_v4(weights+extract)" : "k_tgsw_dfa_v4(weights)")
+                           : (last ? "k_tgsw_dfa_v4(extract)" : "k_tgsw_dfa_v4"));
     with_flag(first, [&](auto fi) {
         with_flag(last, [&](auto la) {
-            hipLaunchKernelGGL((k_tgsw_dfa_v4<decltype(fi)::value, decltype(la)::value>), dim3(a.B * a.n_live),
-                               dim3(kV4Threads), 0, s, g, a);
+            with_flag(tw, [&](auto we) {
+                hipLaunchKernelGGL((k_tgsw_dfa_v4<decltype(fi)::value, decltype(la)::value, decltype(we)::value>),
+                                   dim3(a.B * a.n_live), dim3(kV4Threads), 0, s, g, a);
+            });
         });
     });
     return hipGetLastError();

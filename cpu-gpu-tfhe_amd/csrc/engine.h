@@ -262,6 +262,11 @@ struct TgswDfaStep {
     int n_out = 1;
     long u_stride = 0;
     int32_t *u_a = nullptr, *u_b = nullptr;
+    // transition weights, both or neither: w_val [Q][2] Torus32, w_pos the one
+    // word of this step's coefficient position p.  d_b gains w_val[s][b] X^p on its b polynomial, a
+    // state copies only when its two weights are equal too, a p outside [0, kN) makes the step
+    // weightless; n_out may be up to 64 then.
+    const int32_t *w_val = nullptr, *w_pos = nullptr;
 };
 hipError_t launch_tgsw_dfa_v4(const DeviceKey &key, const uint32_t *set, const TgswDfaStep &a, bool first, bool last,
                               hipStream_t s);

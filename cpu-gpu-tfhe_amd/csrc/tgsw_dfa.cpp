@@ -3,6 +3,8 @@
 // kernel is k_tgsw_dfa_v4 (blind_rotate_v4.hip), launched once per input bit; this file holds the
 // automaton (transitions, live sets, state scratch), the argument checks, the slicing, the host
 // staging and the host-only builders.  It reaches a context only through tfhe_amd_internal_frame.
+// The weighted runs (tfhe_amd_wfa_*) are the same path with two more arrays: every
+// transition adds a plaintext monomial, so the result carries values computed along the path.
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -26,6 +28,7 @@ using namespace tfhe_amd;
 
 namespace {
 constexpr int kMaxStates = 64, kMaxLen = 1024, kMaxOut = 16;
+constexpr int kMaxOutWeighted = 64;   // the weighted runs: one output per bit of a 64-bit result
 constexpr size_t kScratchBytes = (size_t)256 << 20;   // both state buffers together
 }  // namespace
 
@@ -76,13 +79,30 @@ struct RunJob {
     int B, len, n_fin, fin_rows, n_out;
     const int32_t *sel, *fin, *fin_index;
     int32_t *out_a, *out_b;
+    // the weighted forms (tfhe_amd_wfa_run_*): w_val [Q][2], w_pos [len], shared by the queries
+    bool weighted = false;
+    const int32_t *w_val = nullptr, *w_pos = nullptr;
 };
 
+RunJob weighted_job(RunJob j, const int32_t *w_val, const int32_t *w_pos) {
+    j.weighted = true;
+    j.w_val = w_val;
+    j.w_pos = w_pos;
+    return j;
+}
+
 // shape checks shared by the device and host forms (no pointer is read)
-bool run_shape_ok(const TfheAmdTgsw *set, const TfheAmdDfa *dfa, int B, int len, int n_fin, int fin_rows, int n_out) {
-    if (!set || !dfa || B < 0 || len < 1 || len > dfa->max_len || n_fin < 1) return false;
-    if ((fin_rows != 1 && fin_rows != 2) || n_out < 1 || n_out > kMaxOut) return false;
-    return (long)B * n_out <= 0x3fffffffL && (long)B * len <= 0x3fffffffL;
+bool run_shape_ok(const RunJob &j) {
+    if (!j.set || !j.dfa || j.B < 0 || j.len < 1 || j.len > j.dfa->max_len || j.n_fin < 1) return false;
+    if ((j.fin_rows != 1 && j.fin_rows != 2) || j.n_out < 1 || j.n_out > (j.weighted ? kMaxOutWeighted : kMaxOut))
+        return false;
+    return (long)j.B * j.n_out <= 0x3fffffffL && (long)j.B * j.len <= 0x3fffffffL;
+}
+
+// the pointers every run with B > 0 needs (none is read here)
+bool run_pointers_ok(const RunJob &j) {
+    if (!j.sel || !j.fin || !j.out_a || !j.out_b) return false;
+    return !j.weighted || (j.w_val && j.w_pos);
 }
 
 int run_in_frame(const ContextFrame &f, void *arg) {
@@ -121,6 +141,7 @@ int run_in_frame(const ContextFrame &f, void *arg) {
     a.fin_rows = j.fin_rows;
     a.n_out = j.n_out;
     a.u_stride = j.B;
+    a.w_val = j.weighted ? j.w_val : nullptr;
     for (int q0 = 0; q0 < j.B; q0 += Bs_max) {
         a.B = j.B - q0 < Bs_max ? j.B - q0 : Bs_max;
         a.fin_index = j.fin_index ? j.fin_index + q0 : nullptr;
@@ -129,6 +150,7 @@ int run_in_frame(const ContextFrame &f, void *arg) {
         // step t reads bit t - 1 and computes the states of R_{t-1} from buffer (t + 1) & 1 into t & 1
         for (int t = j.len; t >= 1; --t) {
             a.sel = j.sel + (size_t)q0 * j.len + (t - 1);
+            a.w_pos = j.weighted ? j.w_pos + (t - 1) : nullptr;
             a.live = d->d_tab + 2 * d->Q + d->off[t - 1];
             a.n_live = d->off[t] - d->off[t - 1];
             a.src = buf[(t + 1) & 1];
@@ -144,11 +166,11 @@ int run_in_frame(const ContextFrame &f, void *arg) {
 
 int run_dev(TfheAmdContext *c, const RunJob &job, void *stream) {
     const RunJob &j = job;
-    if (!c || !run_shape_ok(j.set, j.dfa, j.B, j.len, j.n_fin, j.fin_rows, j.n_out)) return TFHE_AMD_E_ARG;
+    if (!c || !run_shape_ok(j)) return TFHE_AMD_E_ARG;
     const int dev = tfhe_amd_context_device(c);
     if (j.set->device != dev || j.set->count <= 0 || j.dfa->device != dev || !j.dfa->d_tab) return TFHE_AMD_E_ARG;
     if (j.B == 0) return TFHE_AMD_OK;
-    if (!j.sel || !j.fin || !j.out_a || !j.out_b) return TFHE_AMD_E_ARG;
+    if (!run_pointers_ok(j)) return TFHE_AMD_E_ARG;
     RunJob copy = j;
     return tfhe_amd_internal_frame(c, stream, j.ks ? j.B * j.n_out : 0, run_in_frame, &copy);
 }
@@ -165,10 +187,16 @@ int run_host_in_frame(const ContextFrame &f, void *arg) {
     const size_t n_sel = (size_t)j.B * j.len, n_finw = (size_t)j.n_fin * j.dfa->Q * j.fin_rows * kN;
     const size_t n_res = (size_t)j.n_out * j.B, row = j.ks ? kn : kN;
     DevBufs bufs;
-    int32_t *d_sel, *d_fin, *d_idx = nullptr, *d_a, *d_b;
+    int32_t *d_sel, *d_fin, *d_idx = nullptr, *d_a, *d_b, *d_wv = nullptr, *d_wp = nullptr;
     HIPCHK(bufs.get(&d_sel, n_sel));
     HIPCHK(bufs.get(&d_fin, n_finw));
     if (j.fin_index) HIPCHK(bufs.get(&d_idx, (size_t)j.B));
+    if (j.weighted) {
+        HIPCHK(bufs.get(&d_wv, (size_t)2 * j.dfa->Q));
+        HIPCHK(bufs.get(&d_wp, (size_t)j.len));
+        HIPCHK(hipMemcpyAsync(d_wv, j.w_val, sizeof(int32_t) * 2 * j.dfa->Q, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_wp, j.w_pos, sizeof(int32_t) * j.len, hipMemcpyHostToDevice, s));
+    }
     HIPCHK(bufs.get(&d_a, n_res * row));
     HIPCHK(bufs.get(&d_b, n_res));
     HIPCHK(hipMemcpyAsync(d_sel, j.sel, sizeof(int32_t) * n_sel, hipMemcpyHostToDevice, s));
@@ -178,6 +206,8 @@ int run_host_in_frame(const ContextFrame &f, void *arg) {
     dj.sel = d_sel;
     dj.fin = d_fin;
     dj.fin_index = d_idx;
+    dj.w_val = d_wv;
+    dj.w_pos = d_wp;
     dj.out_a = d_a;
     dj.out_b = d_b;
     hipError_t sync = hipSuccess;
@@ -194,13 +224,16 @@ int run_host_in_frame(const ContextFrame &f, void *arg) {
 }
 
 int run_host(TfheAmdContext *c, const RunJob &j) {
-    if (!c || !run_shape_ok(j.set, j.dfa, j.B, j.len, j.n_fin, j.fin_rows, j.n_out)) return TFHE_AMD_E_ARG;
+    if (!c || !run_shape_ok(j)) return TFHE_AMD_E_ARG;
     const int dev = tfhe_amd_context_device(c);
     if (j.set->device != dev || j.set->count <= 0 || j.dfa->device != dev || !j.dfa->d_tab) return TFHE_AMD_E_ARG;
     if (j.B == 0) return TFHE_AMD_OK;
-    if (!j.sel || !j.fin || !j.out_a || !j.out_b) return TFHE_AMD_E_ARG;
+    if (!run_pointers_ok(j)) return TFHE_AMD_E_ARG;
     for (size_t k = 0; k < (size_t)j.B * j.len; ++k)
         if (j.sel[k] < 0 || j.sel[k] >= j.set->count) return TFHE_AMD_E_ARG;
+    if (j.weighted)
+        for (int i = 0; i < j.len; ++i)
+            if (j.w_pos[i] < 0 || j.w_pos[i] >= kN) return TFHE_AMD_E_ARG;
     if (j.fin_index)
         for (int q = 0; q < j.B; ++q)
             if (j.fin_index[q] < 0 || j.fin_index[q] >= j.n_fin) return TFHE_AMD_E_ARG;
@@ -307,6 +340,40 @@ extern "C" int tfhe_amd_dfa_run_host(TfheAmdContext *ctx, TfheAmdTgsw *set, Tfhe
     return run_host(ctx, RunJob{set, dfa, true, B, len, n_fin, fin_rows, n_out, sel, fin, fin_index, res_a, res_b});
 }
 
+// ---- weighted runs: the same path with the transition weights behind sel
+
+extern "C" int tfhe_amd_wfa_run_woks_dev(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                                         const int32_t *sel, const int32_t *w_val, const int32_t *w_pos, int n_fin,
+                                         int fin_rows, const int32_t *fin, const int32_t *fin_index, int n_out,
+                                         int32_t *u_a, int32_t *u_b, void *stream) {
+    return run_dev(ctx, weighted_job(RunJob{set, dfa, false, B, len, n_fin, fin_rows, n_out, sel, fin, fin_index, u_a, u_b},
+                                     w_val, w_pos), stream);
+}
+
+extern "C" int tfhe_amd_wfa_run_dev(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                                    const int32_t *sel, const int32_t *w_val, const int32_t *w_pos, int n_fin,
+                                    int fin_rows, const int32_t *fin, const int32_t *fin_index, int n_out,
+                                    int32_t *res_a, int32_t *res_b, void *stream) {
+    return run_dev(ctx, weighted_job(RunJob{set, dfa, true, B, len, n_fin, fin_rows, n_out, sel, fin, fin_index, res_a, res_b},
+                                     w_val, w_pos), stream);
+}
+
+extern "C" int tfhe_amd_wfa_run_woks_host(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                                          const int32_t *sel, const int32_t *w_val, const int32_t *w_pos, int n_fin,
+                                          int fin_rows, const int32_t *fin, const int32_t *fin_index, int n_out,
+                                          int32_t *u_a, int32_t *u_b) {
+    return run_host(ctx, weighted_job(RunJob{set, dfa, false, B, len, n_fin, fin_rows, n_out, sel, fin, fin_index, u_a, u_b},
+                                      w_val, w_pos));
+}
+
+extern "C" int tfhe_amd_wfa_run_host(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                                     const int32_t *sel, const int32_t *w_val, const int32_t *w_pos, int n_fin,
+                                     int fin_rows, const int32_t *fin, const int32_t *fin_index, int n_out,
+                                     int32_t *res_a, int32_t *res_b) {
+    return run_host(ctx, weighted_job(RunJob{set, dfa, true, B, len, n_fin, fin_rows, n_out, sel, fin, fin_index, res_a, res_b},
+                                      w_val, w_pos));
+}
+
 // ---- builders (host only)
 
 extern "C" int tfhe_amd_dfa_build_compare(int32_t *next, int *start, int32_t *cls) {
@@ -368,6 +435,80 @@ extern "C" int tfhe_amd_dfa_simulate(int n_states, int start, const int32_t *nex
     int s = start;
     for (int i = 0; i < len; ++i) {
         if (bits[i] != 0 && bits[i] != 1) return TFHE_AMD_E_ARG;
+        s = next[2 * s + bits[i]];
+    }
+    return s;
+}
+
+// ---- weighted builders (host only)
+
+extern "C" int tfhe_amd_wfa_build_max(int d, int want_max, int32_t *next, int *start, int32_t *w_val, int32_t *w_pos) {
+    if (!next || !start || !w_val || !w_pos || d < 1 || d > 64) return TFHE_AMD_E_ARG;
+    // 0: x = y so far, an x bit comes; 1 / 2: x = y so far and this pair's x bit read, 0 / 1;
+    // 3 / 4: x < y decided, an x / a y bit comes; 5 / 6: x > y decided, an x / a y bit comes.
+    // The decided states alternate so that the position-independent weights tell the bits apart.
+    enum { EQ, MID0, MID1, LTX, LTY, GTX, GTY };
+    const int32_t t[7][2] = {{MID0, MID1}, {EQ, LTX}, {GTX, EQ}, {LTY, LTY}, {LTX, LTX}, {GTY, GTY}, {GTX, GTX}};
+    memcpy(next, t, sizeof(t));
+    *start = EQ;
+    const int32_t one = 1 << 30;
+    memset(w_val, 0, sizeof(int32_t) * 14);
+    // the weight sits on the transition that knows the result's bit: in an undecided pair the y bit's
+    // (x = y = 1; x < y gives y = 1 to the maximum, x > y gives x = 1 to it, and 0 to the minimum)
+    w_val[2 * MID1 + 1] = one;
+    if (want_max) {
+        w_val[2 * MID0 + 1] = one;
+        w_val[2 * MID1 + 0] = one;
+    }
+    // decided: x < y takes y's bits for the maximum and x's for the minimum, x > y the other way
+    w_val[2 * (want_max ? LTY : LTX) + 1] = one;
+    w_val[2 * (want_max ? GTX : GTY) + 1] = one;
+    for (int k = 0; k < d; ++k) w_pos[2 * k] = w_pos[2 * k + 1] = d - 1 - k;   // pair k holds bit d - 1 - k
+    return 7;
+}
+
+extern "C" int tfhe_amd_wfa_build_popcount(int len, int p, int32_t *next, int *start, int32_t *w_val, int32_t *w_pos) {
+    if (!next || !start || !w_val || !w_pos || (p != 2 && p != 4 && p != 8 && p != 16) || len < 1 || len > p - 1)
+        return TFHE_AMD_E_ARG;
+    next[0] = next[1] = 0;
+    *start = 0;
+    w_val[0] = 0;
+    w_val[1] = (int32_t)((1ll << 32) / (2 * p));   // one step of the LUT digit (2 c + 1) / (4 p)
+    for (int i = 0; i < len; ++i) w_pos[i] = 0;
+    return 1;
+}
+
+extern "C" int tfhe_amd_wfa_build_first_one(int len, int32_t *next, int *start, int32_t *w_val, int32_t *w_pos) {
+    if (!next || !start || !w_val || !w_pos || len < 1 || len > 64) return TFHE_AMD_E_ARG;
+    // 0: no set bit seen; 1: seen (absorbing, weightless)
+    const int32_t t[2][2] = {{0, 1}, {1, 1}};
+    memcpy(next, t, sizeof(t));
+    *start = 0;
+    memset(w_val, 0, sizeof(int32_t) * 4);
+    w_val[1] = 1 << 30;
+    for (int i = 0; i < len; ++i) w_pos[i] = i;
+    return 2;
+}
+
+extern "C" int tfhe_amd_wfa_fin_fill(int n_states, int n_out, int32_t value, int32_t *fin) {
+    if (!fin || n_states < 1 || n_states > kMaxStates || n_out < 1 || n_out > kMaxOutWeighted) return TFHE_AMD_E_ARG;
+    memset(fin, 0, sizeof(int32_t) * (size_t)n_states * kN);
+    for (int s = 0; s < n_states; ++s)
+        for (int f = 0; f < n_out; ++f) fin[(size_t)s * kN + f] = value;
+    return TFHE_AMD_OK;
+}
+
+extern "C" int tfhe_amd_wfa_simulate(int n_states, int start, const int32_t *next, const int32_t *w_val,
+                                     const int32_t *w_pos, int len, const int32_t *bits, int32_t *poly) {
+    if (!next || !w_val || !poly || n_states < 1 || n_states > kMaxStates || start < 0 || start >= n_states || len < 0 ||
+        (len > 0 && (!bits || !w_pos)) || !next_ok(n_states, next))
+        return TFHE_AMD_E_ARG;
+    for (int i = 0; i < len; ++i)
+        if ((bits[i] != 0 && bits[i] != 1) || w_pos[i] < 0 || w_pos[i] >= kN) return TFHE_AMD_E_ARG;
+    memset(poly, 0, sizeof(int32_t) * kN);
+    int s = start;
+    for (int i = 0; i < len; ++i) {
+        poly[w_pos[i]] = (int32_t)((uint32_t)poly[w_pos[i]] + (uint32_t)w_val[2 * s + bits[i]]);
         s = next[2 * s + bits[i]];
     }
     return s;

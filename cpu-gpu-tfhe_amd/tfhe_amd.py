@@ -165,6 +165,18 @@ def _load():
     L.tfhe_amd_dfa_build_at_least.argtypes = [ctypes.c_int, _I32P, ctypes.POINTER(ctypes.c_int)]
     L.tfhe_amd_dfa_fin_fill.argtypes = [ctypes.c_int, ctypes.c_int, _I32P, _I32P]
     L.tfhe_amd_dfa_simulate.argtypes = [ctypes.c_int, ctypes.c_int, _I32P, ctypes.c_int, _I32P]
+    # weighted runs of a leveled automaton (tfhe_amd_wfa_*)
+    for f in ("tfhe_amd_wfa_run_woks_dev", "tfhe_amd_wfa_run_dev"):
+        getattr(L, f).argtypes = ([_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _VP, _VP, _VP, ctypes.c_int, ctypes.c_int,
+                                   _VP, _VP, ctypes.c_int, _VP, _VP, _VP])
+    for f in ("tfhe_amd_wfa_run_woks_host", "tfhe_amd_wfa_run_host"):
+        getattr(L, f).argtypes = ([_VP, _VP, _VP, ctypes.c_int, ctypes.c_int, _I32P, _I32P, _I32P, ctypes.c_int,
+                                   ctypes.c_int, _I32P, _I32P, ctypes.c_int, _I32P, _I32P])
+    L.tfhe_amd_wfa_build_max.argtypes = [ctypes.c_int, ctypes.c_int, _I32P, ctypes.POINTER(ctypes.c_int), _I32P, _I32P]
+    L.tfhe_amd_wfa_build_popcount.argtypes = [ctypes.c_int, ctypes.c_int, _I32P, ctypes.POINTER(ctypes.c_int), _I32P, _I32P]
+    L.tfhe_amd_wfa_build_first_one.argtypes = [ctypes.c_int, _I32P, ctypes.POINTER(ctypes.c_int), _I32P, _I32P]
+    L.tfhe_amd_wfa_fin_fill.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int32, _I32P]
+    L.tfhe_amd_wfa_simulate.argtypes = [ctypes.c_int, ctypes.c_int, _I32P, _I32P, _I32P, ctypes.c_int, _I32P, _I32P]
     # packing key switch (tfhe_amd_pack_*)
     L.tfhe_amd_pack_key_generate.argtypes = [_VP, _I32P]
     L.tfhe_amd_tlwe_phase_polys.argtypes = [_VP, ctypes.c_int, _I32P, _I32P]
@@ -701,6 +713,62 @@ def dfa_simulate(next, start, bits):
                       "dfa_simulate")
 
 
+def _wfa_fin(n_states, n_out, value):
+    fin = np.zeros((1, n_states, 1, N), np.int32)
+    _check(lib.tfhe_amd_wfa_fin_fill(n_states, n_out, int(value), _p(fin)), "wfa_fin_fill")
+    return fin
+
+
+def wfa_max(d, want_max=True):
+    """tfhe_amd_wfa_build_max: max (or min) of two d-bit integers over the word x_{d-1}, y_{d-1}, ...,
+    x_0, y_0 -> (next [7][2], start, (w_val [7][2], w_pos [2 d]), fin [1][7][1][1024]); with n_out = d
+    output f is bit f of the result as +-1/8"""
+    d = int(d)
+    next, w_val, w_pos, start = (np.zeros((7, 2), np.int32), np.zeros((7, 2), np.int32),
+                                 np.zeros(2 * max(d, 1), np.int32), ctypes.c_int())
+    _dfa_built(lib.tfhe_amd_wfa_build_max(d, int(bool(want_max)), _p(next), ctypes.byref(start), _p(w_val), _p(w_pos)),
+               "wfa_build_max")
+    return next, start.value, (w_val, w_pos), _wfa_fin(7, d, -(1 << 29))
+
+
+def wfa_popcount(length, p):
+    """tfhe_amd_wfa_build_popcount: the number of set bits of a word of `length` <= p - 1 bits as a LUT
+    digit modulo p -> (next [1][2], start, (w_val [1][2], w_pos [length]), fin [1][1][1][1024]); the
+    single output is the digit (2 c + 1) / (4 p) of the count c"""
+    length, p = int(length), int(p)
+    next, w_val, w_pos, start = (np.zeros((1, 2), np.int32), np.zeros((1, 2), np.int32),
+                                 np.zeros(max(length, 1), np.int32), ctypes.c_int())
+    _dfa_built(lib.tfhe_amd_wfa_build_popcount(length, p, _p(next), ctypes.byref(start), _p(w_val), _p(w_pos)),
+               "wfa_build_popcount")
+    return next, start.value, (w_val, w_pos), _wfa_fin(1, 1, (1 << 32) // (4 * p))
+
+
+def wfa_first_one(length):
+    """tfhe_amd_wfa_build_first_one: the one-hot position of the first set bit of a word of `length`
+    <= 64 bits -> (next [2][2], start, (w_val [2][2], w_pos [length]), fin [1][2][1][1024]); with
+    n_out = length output f is 1 (as +-1/8) exactly when bit f is the first set bit"""
+    length = int(length)
+    next, w_val, w_pos, start = (np.zeros((2, 2), np.int32), np.zeros((2, 2), np.int32),
+                                 np.zeros(max(length, 1), np.int32), ctypes.c_int())
+    _dfa_built(lib.tfhe_amd_wfa_build_first_one(length, _p(next), ctypes.byref(start), _p(w_val), _p(w_pos)),
+               "wfa_build_first_one")
+    return next, start.value, (w_val, w_pos), _wfa_fin(2, length, -(1 << 29))
+
+
+def wfa_simulate(next, start, weights, bits):
+    """tfhe_amd_wfa_simulate: (the state after the plain word bits, poly [1024] = the sum of the
+    weights w_val[s_i][bit_i] X^{w_pos[i]} along its path); weights = (w_val, w_pos)"""
+    next, bits = i32(next), i32(np.asarray(bits).reshape(-1))
+    w_val, w_pos = i32(weights[0]), i32(np.asarray(weights[1]).reshape(-1))
+    if w_val.shape != next.shape or w_pos.shape[0] < bits.shape[0]:
+        raise TfheAmdError(f"need w_val {next.shape} and w_pos of at least {bits.shape[0]} entries, got {w_val.shape}, "
+                           f"{w_pos.shape}")
+    poly = np.zeros(N, np.int32)
+    s = _dfa_built(lib.tfhe_amd_wfa_simulate(next.shape[0], int(start), _p(next), _p(w_val), _p(w_pos), bits.shape[0],
+                                             _p(bits), _p(poly)), "wfa_simulate")
+    return s, poly
+
+
 class PackKey:
     """TfheAmdPackKey: the packing key imported to a context's device (Context.pack_key_import);
     close() frees it.  It does not depend on the context's lifetime."""
@@ -1074,10 +1142,12 @@ class Context:
         caller's own) -> Dfa on this context's device, for words of up to max_len bits"""
         return Dfa._create(self.h, next, start, max_len)
 
-    def dfa_run_host(self, tset, dfa, sel, fin, fin_index=None, n_out=1, woks=False):
+    def dfa_run_host(self, tset, dfa, sel, fin, fin_index=None, n_out=1, woks=False, weights=None):
         """tfhe_amd_dfa_run[_woks]_host: sel [B][len] selector indices (bit 0 first), fin
         [n_fin][n_states][fin_rows][1024] final weights -> (r_a [n_out][B][500], r_b [n_out][B]), or
-        with woks the extracted samples (u_a [n_out][B][1024], u_b [n_out][B])"""
+        with woks the extracted samples (u_a [n_out][B][1024], u_b [n_out][B]).
+        weights = (w_val [n_states][2], w_pos [len]): the weighted run tfhe_amd_wfa_run[_woks]_host
+        (wfa_max, wfa_popcount, wfa_first_one or the caller's own), n_out up to 64"""
         sel = i32(sel); fin = i32(fin)
         if sel.ndim != 2 or fin.ndim != 4 or fin.shape[1] != dfa.n_states or fin.shape[3] != N:
             raise TfheAmdError(f"need sel [B][len] and fin [n_fin][{dfa.n_states}][fin_rows][1024], got {sel.shape}, "
@@ -1090,13 +1160,24 @@ class Context:
         n_out = int(n_out)
         r_a = np.zeros((max(n_out, 1), B, N if woks else n_lwe), np.int32)
         r_b = np.zeros((max(n_out, 1), B), np.int32)
+        if weights is not None:
+            w_val, w_pos = i32(weights[0]), i32(weights[1])
+            if w_val.shape != (dfa.n_states, 2) or w_pos.shape != (length,):
+                raise TfheAmdError(f"weights: need w_val [{dfa.n_states}][2] and w_pos [{length}], got {w_val.shape}, "
+                                   f"{w_pos.shape}")
+            name = "wfa_run" + ("_woks" if woks else "") + "_host"
+            _check(getattr(lib, "tfhe_amd_" + name)(self.h, tset.h, dfa.h, B, length, _p(sel), _p(w_val), _p(w_pos),
+                                                    n_fin, rows, _p(fin), _p(idx), n_out, _p(r_a), _p(r_b)), name)
+            return r_a, r_b
         name = "dfa_run" + ("_woks" if woks else "") + "_host"
         _check(getattr(lib, "tfhe_amd_" + name)(self.h, tset.h, dfa.h, B, length, _p(sel), n_fin, rows, _p(fin),
                                                 _p(idx), n_out, _p(r_a), _p(r_b)), name)
         return r_a, r_b
 
-    def dfa_run_dev(self, tset, dfa, sel, fin, out_a, out_b, fin_index=None, n_out=1, woks=False, stream=None):
-        """tfhe_amd_dfa_run[_woks]_dev on torch tensors (shapes as dfa_run_host); asynchronous"""
+    def dfa_run_dev(self, tset, dfa, sel, fin, out_a, out_b, fin_index=None, n_out=1, woks=False, stream=None,
+                    weights=None):
+        """tfhe_amd_dfa_run[_woks]_dev on torch tensors (shapes as dfa_run_host); asynchronous.
+        weights = (w_val, w_pos) GPU tensors: tfhe_amd_wfa_run[_woks]_dev"""
         if sel is None or sel.dim() != 2 or fin is None or fin.dim() != 4:
             raise TfheAmdError("need GPU tensors sel [B][len] and fin [n_fin][n_states][fin_rows][1024]")
         B, length = sel.shape
@@ -1106,8 +1187,17 @@ class Context:
                  ("out_a", out_a, (max(n_out, 1), B, N if woks else n_lwe)), ("out_b", out_b, (max(n_out, 1), B))]
         if fin_index is not None:
             named.append(("fin_index", fin_index, (B,)))
+        if weights is not None:
+            named += [("w_val", weights[0], (dfa.n_states, 2)), ("w_pos", weights[1], (length,))]
         for name, t, shape in named:
             self._dev_check(t, shape, name)
+        if weights is not None:
+            name = "wfa_run" + ("_woks" if woks else "") + "_dev"
+            _check(getattr(lib, "tfhe_amd_" + name)(self.h, tset.h, dfa.h, B, length, sel.data_ptr(),
+                                                    weights[0].data_ptr(), weights[1].data_ptr(), n_fin, rows,
+                                                    fin.data_ptr(), None if fin_index is None else fin_index.data_ptr(),
+                                                    n_out, out_a.data_ptr(), out_b.data_ptr(), stream), name)
+            return
         name = "dfa_run" + ("_woks" if woks else "") + "_dev"
         _check(getattr(lib, "tfhe_amd_" + name)(self.h, tset.h, dfa.h, B, length, sel.data_ptr(), n_fin, rows,
                                                 fin.data_ptr(), None if fin_index is None else fin_index.data_ptr(),

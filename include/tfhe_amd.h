@@ -471,6 +471,76 @@ int tfhe_amd_dfa_build_at_least(int t, int32_t *next, int *start);
 int tfhe_amd_dfa_fin_fill(int n_states, int n_out, const int32_t *values, int32_t *fin);
 int tfhe_amd_dfa_simulate(int n_states, int start, const int32_t *next, int len, const int32_t *bits);
 
+/* ---- Weighted runs of a leveled automaton: every transition adds a plaintext
+ * monomial to the accumulator, so a run returns values computed from the word and not only a class of
+ * it.  The automaton is a TfheAmdDfa as above; a run takes two more arrays, shared by its queries:
+ *   w_val [n_states][2]: a Torus32 scalar per (state, bit);
+ *   w_pos [len]: the coefficient position of step i, in [0, 1024).
+ * For j = len .. 1, i = j - 1, p = w_pos[i] and every state s of R_{j-1}:
+ *   d_b = ACC_j[next[s][b]] + (0, w_val[s][b] X^p)   (the b polynomial's coefficient p alone)
+ *   ACC_{j-1}[s] = d0 + C_i (x) (d1 - d0 + 2^11 on every word)
+ * so the phase of ACC_0[start] is fin[s_len] + sum_i w_val[s_i][bit_i] X^{w_pos[i]} plus noise, s_i
+ * the state before bit i is read.  The weights are plaintext and add no noise.  A state copies its
+ * operand (d0 + w0 X^p) only when next0 == next1 and w0 == w1; a selector outside [0, count) gives
+ * d0 + w0 X^p too.  All-zero w_val gives exactly the words of tfhe_amd_dfa_run_*.
+ *
+ * tfhe_amd_wfa_run_*: the arguments, layouts, slicing, ordering and refusals of the tfhe_amd_dfa_run_*
+ * form of the same suffix, with w_val and w_pos behind sel (device arrays in the _dev forms, host
+ * arrays in the _host forms) and n_out in [1, 64].  Null weight arrays with B > 0 are refused.  In the
+ * _dev forms a w_pos[i] outside [0, 1024) makes step i weightless (both weights count as 0); the
+ * _host forms return TFHE_AMD_E_ARG for it and write nothing.
+ * tfhe_amd_last_kernels reports "k_tgsw_dfa_v4(weights+tw)" for the last bit, "k_tgsw_dfa_v4(tw)" for
+ * the bits in between, "k_tgsw_dfa_v4(tw+extract)" for bit 0 and "k_tgsw_dfa_v4(weights+tw+extract)"
+ * for len = 1; then the key switch's own name. */
+int tfhe_amd_wfa_run_woks_dev(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                              const int32_t *sel, const int32_t *w_val, const int32_t *w_pos, int n_fin,
+                              int fin_rows, const int32_t *fin, const int32_t *fin_index, int n_out, int32_t *u_a,
+                              int32_t *u_b, void *stream);
+int tfhe_amd_wfa_run_dev(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                         const int32_t *sel, const int32_t *w_val, const int32_t *w_pos, int n_fin, int fin_rows,
+                         const int32_t *fin, const int32_t *fin_index, int n_out, int32_t *res_a, int32_t *res_b,
+                         void *stream);
+int tfhe_amd_wfa_run_woks_host(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                               const int32_t *sel, const int32_t *w_val, const int32_t *w_pos, int n_fin,
+                               int fin_rows, const int32_t *fin, const int32_t *fin_index, int n_out, int32_t *u_a,
+                               int32_t *u_b);
+int tfhe_amd_wfa_run_host(TfheAmdContext *ctx, TfheAmdTgsw *set, TfheAmdDfa *dfa, int B, int len,
+                          const int32_t *sel, const int32_t *w_val, const int32_t *w_pos, int n_fin, int fin_rows,
+                          const int32_t *fin, const int32_t *fin_index, int n_out, int32_t *res_a, int32_t *res_b);
+
+/* Weighted builders (host only, no GPU): they fill next [n_states][2], *start, w_val [n_states][2] and
+ * w_pos [len] and return the number of states, or TFHE_AMD_E_ARG for a null pointer or a parameter
+ * outside its range.
+ * tfhe_amd_wfa_build_max: max(x, y) (want_max != 0) or min(x, y) of two d-bit integers, 1 <= d <= 64,
+ *   over the word x_{d-1}, y_{d-1}, ..., x_0, y_0 (len = 2 d): 7 states, next and w_val [7][2], w_pos
+ *   [2 d].  State 0: equal so far; 1 / 2: equal so far and this pair's x bit read, 0 / 1; 3 / 4: x < y
+ *   decided and an x / a y bit comes next; 5 / 6: x > y decided likewise (w_val does not depend on the
+ *   position, so the decided states tell an x bit from a y bit).  The weight is 2^30 on exactly the
+ *   transitions where the result's bit is 1, at coefficient d - 1 - k for the k-th pair read (bit
+ *   d - 1 - k of the integers).  With fin = -2^29 at the coefficients 0 .. d - 1 of every state
+ *   (tfhe_amd_wfa_fin_fill) output f is bit f of the result in the gate encoding +-1/8, n_out = d.
+ *   At most 5 products per pair.
+ * tfhe_amd_wfa_build_popcount: the number of set bits of a word of len bits as a LUT digit modulo p,
+ *   p in {2, 4, 8, 16}, 1 <= len <= p - 1: one state, w_val[0][1] = 2^32 / (2 p), every w_pos = 0.
+ *   With fin = 2^32 / (4 p) at coefficient 0 the single output is the digit (2 c + 1) / (4 p) of the
+ *   count c, an input of tfhe_amd_bootstrap_lut_*.
+ * tfhe_amd_wfa_build_first_one: the one-hot position of the first set bit of a word of len bits,
+ *   1 <= len <= 64: two states (0: none seen, 1: seen, absorbing), w_val[0][1] = 2^30, w_pos[i] = i.
+ *   With fin = -2^29 at the coefficients 0 .. len - 1 output f is 1 exactly when bit f is the first
+ *   set bit, in the gate encoding, n_out = len.
+ * tfhe_amd_wfa_fin_fill: fin [n_states][1024] with `value` at the coefficients 0 .. n_out - 1 of
+ *   every state and zeros elsewhere, 1 <= n_out <= 64; returns TFHE_AMD_OK.
+ * tfhe_amd_wfa_simulate: poly [1024] = sum_i w_val[s_i][bits[i]] X^{w_pos[i]} (wrapping) for the plain
+ *   word bits [len] (bit 0 first, len >= 0); returns the final state, or TFHE_AMD_E_ARG for a bit
+ *   outside {0, 1}, a w_pos entry outside [0, 1024), a transition outside [0, n_states) and bad
+ *   shapes, with poly untouched. */
+int tfhe_amd_wfa_build_max(int d, int want_max, int32_t *next, int *start, int32_t *w_val, int32_t *w_pos);
+int tfhe_amd_wfa_build_popcount(int len, int p, int32_t *next, int *start, int32_t *w_val, int32_t *w_pos);
+int tfhe_amd_wfa_build_first_one(int len, int32_t *next, int *start, int32_t *w_val, int32_t *w_pos);
+int tfhe_amd_wfa_fin_fill(int n_states, int n_out, int32_t value, int32_t *fin);
+int tfhe_amd_wfa_simulate(int n_states, int start, const int32_t *next, const int32_t *w_val, const int32_t *w_pos,
+                          int len, const int32_t *bits, int32_t *poly);
+
 /* ---- Packing key switch: computed LWE samples gathered into TLWE ciphertexts.
  * The public functional key switch with f = identity onto coefficient positions: P <= 1024 samples
  * (a_p, b_p) under the n = 500 LWE key become ONE TLWE ciphertext under the keyset's TLWE key whose

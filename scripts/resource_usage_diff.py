@@ -99,14 +99,14 @@ def main():
     # the parent has); later the rows kernels gained the same flag and a trailing kernel argument (the
     # accumulator samples, null in those instantiations): a tree kernel is matched with the parent's by
     # its name, or by its name without the flag (and that argument) where the parent has no kernel of
-    # the full name.
+    # the full name.  The automaton kernel gained a trailing flag the same way (the transition weights).
     parent_names = {short(n) for n in rp}
 
     def key(n):
         k = short(n)
         if k in parent_names:
             return k
-        k = re.sub(r"^(k_blind_rotate_v(?:6p?|4)(?:_rows)?<[^>]*), false>", r"\1>", k)
+        k = re.sub(r"^(k_blind_rotate_v(?:6p?|4)(?:_rows)?<[^>]*|k_tgsw_dfa_v4<[^>]*), false>", r"\1>", k)
         return k if k in parent_names else re.sub(r"^(k_blind_rotate_v(?:6|4)_rows<.*), int const\*\)$", r"\1)", k)
     by_key = {short(n): n for n in rp}
     rt_all = rt
