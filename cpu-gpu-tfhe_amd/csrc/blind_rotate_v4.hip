@@ -302,6 +302,33 @@ __global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4_rows_mk(V4
     }
 }
 
+// Mixed-key circuit levels: k_blind_rotate_v4_rows with the key of the instance's own
+// slot (br_common.h ring_inst_key); flat slot r B + k, guard flags of the same index.  Modes Const, Lut
+// and Many.
+template <int MINW, bool LUT = false, bool MANY = false>
+__global__ __launch_bounds__(kV4Threads, MINW) void k_blind_rotate_v4_rows_mkc(V4Args g, RingInstKeys kr, int B,
+                                                                         long total, const CircRow *__restrict__ rows,
+                                                                         const int32_t *__restrict__ wa,
+                                                                         const int32_t *__restrict__ wb, int32_t mu,
+                                                                         int32_t *__restrict__ u_a,
+                                                                         int32_t *__restrict__ u_b, V4Guard gd) {
+    __shared__ V4Shared sh;
+    bool used = false;
+    for (long slot = blockIdx.x; slot < total; slot += gridDim.x) {
+        if (guard_skip(gd, (size_t)slot)) continue;
+        if (used) __syncthreads();
+        used = true;
+        const int r = (int)(slot / B), k = (int)(slot - (long)r * B);
+        const CircRow row = rows[r];
+        RowTerms t;
+        row_terms(t, row, wa, wb, B, k);
+        V4Args gk = g;
+        gk.bk = ring_inst_key<uint32_t>(kr, k);
+        const LutArgs l = lut_args<LUT, MANY>(rows + r, row, B, k, u_a, u_b);
+        br_v4_body<LUT, MANY, false>(sh, gk, t, mu, u_a + (size_t)slot * kN, u_b + slot, l.tv, l.mo);
+    }
+}
+
 __global__ __launch_bounds__(kV4Threads, 2) void k_blind_rotate_v4_debug(V4Args g, int iters, int32_t *__restrict__ acc,
                                                                       const int32_t *__restrict__ bara) {
     __shared__ V4Shared sh;
@@ -627,6 +654,28 @@ hipError_t launch_blind_rotate_v4_rows_ring(const DeviceKey &key, const RingKeys
             hipLaunchKernelGGL((k_blind_rotate_v4_rows_mk<decltype(f)::value ? 1 : 2, decltype(m)::value>),
                                dim3((unsigned)grid), dim3(kV4Threads), 0, s, v4_args(key), keys, total, rows, wires, lut,
                                mu, u_a, u_b, gd);
+        });
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_blind_rotate_v4_rows_ringc(const DeviceKey &key, const RingInstKeys &keys, int B, int nrows,
+                                             const CircRow *rows, const int32_t *wa, const int32_t *wb, int32_t mu,
+                                             int32_t *u_a, int32_t *u_b, hipStream_t s, BrMode mode, const Guard *guard) {
+    if (B <= 0 || nrows <= 0) return hipSuccess;
+    if (!key.tw2 || !key.tw4 || !keys.bk || !keys.inst_key || keys.n_keys < 1 || !rows || mode == BrMode::Tlwe)
+        return hipErrorInvalidValue;
+    const V4Guard gd = v4_guard(guard);
+    const long total = (long)B * nrows;
+    const long grid = gd.flags && total > kGuardGrid ? kGuardGrid : total < 0x7fffffffL ? total : 0x7fffffffL;
+    trace_kernel(KernelLabel("k_blind_rotate_v4_rows", mode, {"multi-key", "circuit", gd.flags ? "guard" : nullptr}).s);
+    with_mode(mode, [&](auto m) {
+        with_flag(gd.flags != nullptr, [&](auto f) {
+            if constexpr (!mode_tlwe(decltype(m)::value))
+                hipLaunchKernelGGL((k_blind_rotate_v4_rows_mkc<decltype(f)::value ? 1 : 2, mode_lut(decltype(m)::value),
+                                                               mode_many(decltype(m)::value)>),
+                                   dim3((unsigned)grid), dim3(kV4Threads), 0, s, v4_args(key), keys, B, total, rows, wa, wb,
+                                   mu, u_a, u_b, gd);
         });
     });
     return hipGetLastError();

@@ -580,6 +580,30 @@ __global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6_rows_mk(V
                                                          (size_t)r, true, tv);
 }
 
+// Mixed-key circuit levels: k_blind_rotate_v6_rows with the key of the instance's own
+// slot (br_common.h ring_inst_key: clamped, wave-uniform).  Flat slot r B + k, inputs from the wire
+// table, LUT and many-LUT arguments from the row record.  Modes Const, Lut and Many.
+template <int WAVES, bool RREG, bool LUT = false, bool MANY = false>
+__global__ __launch_bounds__(kV6Threads, WAVES) void k_blind_rotate_v6_rows_mkc(V6Args g, RingInstKeys kr, int B,
+                                                                         long base, const CircRow *__restrict__ rows,
+                                                                         const int32_t *__restrict__ wa,
+                                                                         const int32_t *__restrict__ wb, int32_t mu,
+                                                                         int32_t *__restrict__ u_a,
+                                                                         int32_t *__restrict__ u_b) {
+    __shared__ V6Shared sh;
+    const long flat = base + blockIdx.x;          // row-major (row, instance)
+    const int r = (int)(flat / B), k = (int)(flat - (long)r * B);
+    const CircRow row = rows[r];
+    RowTerms t;
+    row_terms(t, row, wa, wb, B, k);
+    V6Args gk = g;
+    gk.bk = ring_inst_key<double2>(kr, k);
+    const size_t slot = (size_t)r * B + k;
+    const LutArgs l = lut_args<LUT, MANY>(rows + r, row, B, k, u_a, u_b);
+    br_v6_body<WAVES, RREG, 1, false, LUT, MANY, false>(sh.ct[0], sh.tw, gk, t, mu, u_a + slot * kN, u_b + slot, slot, true,
+                                                        l.tv, l.mo);
+}
+
 template <bool RREG>
 __global__ __launch_bounds__(kV6Threads, 2) void k_blind_rotate_v6_debug(V6Args g, int iters, int32_t *__restrict__ acc,
                                                                       const int32_t *__restrict__ bara) {
@@ -839,6 +863,34 @@ hipError_t launch_blind_rotate_v6_rows_ring(const DeviceKey &key, const RingKeys
                 hipLaunchKernelGGL((k_blind_rotate_v6_rows_mk<kV6Waves, decltype(f)::value, decltype(m)::value>),
                                    dim3((unsigned)n), dim3(kV6Threads), 0, s, v6_args(key, n, guard), keys, base, rows,
                                    wires, lut, mu, u_a, u_b);
+            });
+        });
+    }
+    return hipGetLastError();
+}
+
+// launch_blind_rotate_v6_rows under the instances' own keys; `key` gives the twiddles and the device
+hipError_t launch_blind_rotate_v6_rows_ringc(const DeviceKey &key, const RingInstKeys &keys, int B, int nrows,
+                                             const CircRow *rows, const int32_t *wa, const int32_t *wb, int32_t mu,
+                                             int32_t *u_a, int32_t *u_b, hipStream_t s, BrMode mode, const Guard *guard) {
+    if (B <= 0 || nrows <= 0) return hipSuccess;
+    if (!key.tw6 || !keys.bk || !keys.inst_key || keys.n_keys < 1 || !rows || mode == BrMode::Tlwe)
+        return hipErrorInvalidValue;
+    const long total = (long)B * nrows, chunk = v6_chunk(key);
+    for (long base = 0; base < total; base += chunk) {
+        const long n = total - base < chunk ? total - base : chunk;
+        if (n > 0x7fffffffL) return hipErrorInvalidValue;
+        const bool rreg = v6_rreg(key, n);
+        trace_kernel(
+            KernelLabel("k_blind_rotate_v6_rows", mode, {"multi-key", "circuit", rreg ? "reg-rotation" : "lds-rotation"}).s);
+        with_mode(mode, [&](auto m) {
+            with_flag(rreg, [&](auto f) {
+                if constexpr (!mode_tlwe(decltype(m)::value))
+                    hipLaunchKernelGGL((k_blind_rotate_v6_rows_mkc<kV6Waves, decltype(f)::value,
+                                                                   mode_lut(decltype(m)::value),
+                                                                   mode_many(decltype(m)::value)>),
+                                       dim3((unsigned)n), dim3(kV6Threads), 0, s, v6_args(key, n, guard), keys, B, base, rows,
+                                       wa, wb, mu, u_a, u_b);
             });
         });
     }

@@ -87,6 +87,13 @@ __device__ __forceinline__ const T *ring_key(const RingKeys &kr, long r) {
     return reinterpret_cast<const T *>((uintptr_t)(((unsigned long long)hi << 32) | lo));
 }
 
+// The key of instance k of a mixed-key circuit level (engine.h RingInstKeys): the same rule, the slot
+// read from inst_key[k].
+template <class T>
+__device__ __forceinline__ const T *ring_inst_key(const RingInstKeys &kr, int k) {
+    return ring_key<T>(RingKeys{kr.bk, kr.inst_key, kr.n_keys}, k);
+}
+
 // The test vector and the extra outputs of one ciphertext.  Compile-time null / default for the
 // constant instantiations, which form no table address.
 struct LutArgs {

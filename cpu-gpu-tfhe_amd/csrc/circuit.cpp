@@ -89,6 +89,7 @@ struct TfheAmdCircuit {
     std::vector<Node> nodes;           // one per wire
     // compiled schedule
     bool compiled = false;
+    uint64_t schedule = 0;   // counts compilations: a run planned against an earlier schedule is refused
     // lut: some row carries a test vector; many: some row is a many-LUT row; urows: u rows the
     // level writes (nrows + the further outputs of its many-LUT rows)
     // select rows: nsel of them from sel0 on in srows / sels, grouped by p; their u rows
@@ -362,6 +363,7 @@ int compile(TfheAmdCircuit *C) {
     // that grew after a run and was then asked for its info would otherwise run on the old block)
     C->states.clear();
     C->compiled = true;
+    C->schedule++;
     return TFHE_AMD_OK;
 }
 
@@ -672,6 +674,29 @@ int tfhe_amd_circuit_run_dev_impl(uint64_t ctx_uid, const DeviceKey &key, int de
 int tfhe_amd_circuit_run_dev_hook(uint64_t ctx_uid, const DeviceKey &key, int device, hipStream_t s,
                                   TfheAmdCircuit *c, int B, int32_t *wa, int32_t *wb, uint32_t *guard_stats,
                                   const CircSelectHook *hook) {
+    return tfhe_amd_circuit_run_dev_hooks(ctx_uid, key, device, s, c, B, wa, wb, guard_stats, hook, nullptr);
+}
+
+// what a mixed-key run needs of the schedule before it enqueues anything (circuit_internal.h)
+int tfhe_amd_internal_circuit_levels(TfheAmdCircuit *c, std::vector<int> *nks, int *has_select, uint64_t *schedule) {
+    if (!c || !nks || !has_select || !schedule) return TFHE_AMD_E_ARG;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->compiled) {
+        const int rc = compile(c);
+        if (rc != TFHE_AMD_OK) return rc;
+    }
+    nks->clear();
+    for (const auto &lv : c->levels) nks->push_back(lv.nrows || lv.nsel ? lv.nks : 0);
+    *has_select = !c->sels.empty();
+    *schedule = c->schedule;
+    return TFHE_AMD_OK;
+}
+
+// level_hook: rotation and key switch of a level's rows through the caller (circuit_internal.h); null
+// on every path but the key ring's
+int tfhe_amd_circuit_run_dev_hooks(uint64_t ctx_uid, const DeviceKey &key, int device, hipStream_t s,
+                                   TfheAmdCircuit *c, int B, int32_t *wa, int32_t *wb, uint32_t *guard_stats,
+                                   const CircSelectHook *hook, const CircLevelHook *level_hook) {
     CircuitDevState *st;
     {
         std::lock_guard<std::mutex> lk(c->mu);
@@ -680,6 +705,8 @@ int tfhe_amd_circuit_run_dev_hook(uint64_t ctx_uid, const DeviceKey &key, int de
             if (rc != TFHE_AMD_OK) return rc;   // (compile drops the states of the earlier schedule)
         }
         if (!c->sels.empty() && !(hook && hook->fn)) return TFHE_AMD_E_ARG;   // before anything is launched
+        // a level hook planned its tables against one schedule: another one is refused here, before any launch
+        if (level_hook && level_hook->fn && level_hook->schedule != c->schedule) return TFHE_AMD_E_ARG;
         auto &slot = c->states[ctx_uid];
         if (!slot) slot.reset(new CircuitDevState());
         st = slot.get();
@@ -729,7 +756,14 @@ int tfhe_amd_circuit_run_dev_hook(uint64_t ctx_uid, const DeviceKey &key, int de
     const CircRow *d_srows = (const CircRow *)((const int32_t *)(d_lin + c->lin.size()) + c->luts.size());
     const CircSel *d_sels = (const CircSel *)(d_srows + c->srows.size());
     for (const auto &lv : c->levels) {
-        if (lv.nrows || lv.nsel) {
+        if (level_hook && level_hook->fn && lv.nrows && !lv.nsel) {
+            const CircLevelJob job{(int)(&lv - c->levels.data()), B, lv.nrows, lv.nks,
+                                   lv.many ? BrMode::Many : lv.lut ? BrMode::Lut : BrMode::Const, d_rows + lv.row0,
+                                   d_ks + lv.ks0, wa, wb, st->u_a, st->u_b,
+                                   guard_stats ? Guard{st->u_flags, guard_stats} : Guard{}};
+            const int rc = level_hook->fn(level_hook->arg, job, s);
+            if (rc != TFHE_AMD_OK) return rc;
+        } else if (lv.nrows || lv.nsel) {
             if (lv.nrows) {
                 const Guard gd = guard_stats ? Guard{st->u_flags, guard_stats} : Guard{};
                 const BrMode mode = lv.many ? BrMode::Many : lv.lut ? BrMode::Lut : BrMode::Const;

@@ -374,6 +374,58 @@ hipError_t launch_blind_rotate_v4_rows_ring(const DeviceKey &key, const RingKeys
 hipError_t launch_ring_linear(int nlin, const CircLin *lin, const RingWires &wires, int32_t *res_a, int32_t *res_b,
                               hipStream_t s);
 
+// ---- mixed-key circuit levels (keyring_circuit.cpp): the rows launch of a circuit
+// level over B instances of several cloud keys.  Flat slot r B + k, wires [W][B] and the row records
+// as in launch_blind_rotate_*_rows (modes Const, Lut and Many); instance k runs under key slot
+// inst_key[k], clamped by the kernel into [0, n_keys) before the slot's key pointer is loaded from bk.
+struct RingInstKeys {
+    const void *const *bk;      // [n_keys] device table of per-slot key pointers (bk_fft / bk_v2)
+    const int32_t *inst_key;    // [B] device
+    int32_t n_keys;
+};
+// geometry, rotation and priority policy of launch_blind_rotate_v6_rows; trace name
+// "k_blind_rotate_v6_rows(<mode>+multi-key+circuit+<rotation>)"
+hipError_t launch_blind_rotate_v6_rows_ringc(const DeviceKey &key, const RingInstKeys &keys, int B, int nrows,
+                                             const CircRow *rows, const int32_t *wa, const int32_t *wb, int32_t mu,
+                                             int32_t *u_a, int32_t *u_b, hipStream_t s, BrMode mode,
+                                             const Guard *guard = nullptr);
+// the exact kernel over the same slots, in guard mode (guard set) or alone; trace name
+// "k_blind_rotate_v4_rows(<mode>+multi-key+circuit[+guard])"
+hipError_t launch_blind_rotate_v4_rows_ringc(const DeviceKey &key, const RingInstKeys &keys, int B, int nrows,
+                                             const CircRow *rows, const int32_t *wa, const int32_t *wb, int32_t mu,
+                                             int32_t *u_a, int32_t *u_b, hipStream_t s, BrMode mode,
+                                             const Guard *guard = nullptr);
+// The key switch of such a level in one launch over all key groups (k_keyswitch_v5 with the tiled
+// lane map).  The instances are sorted by slot: group g holds the instances order[offsets[g] ..
+// offsets[g + 1]), and its lanes, nks offsets[g] + o n_g + j for output o and the group's j-th
+// instance, are cut into M-tiles of ks5_tile_lanes() lanes that never span two groups.  Tile t runs
+// under the ksk5 of tiles[t].slot (clamped into [0, n_keys) before the slot's table entry is loaded),
+// starts at lane tiles[t].first and has tiles[t].live lanes; the padding lanes are never stored.
+// The per-slot table names each member's ksk5 by its distance from base5 in 16-byte units (device
+// allocations are 256-byte aligned): the kernel adds it to the kernel argument base5, so the key
+// stream's loads keep a kernel-argument base like the single-key launches' (a pointer loaded from a
+// table cost the kernel 48 bytes of scratch a lane).
+struct KsTile {
+    int32_t slot, first, live;
+};
+struct RingKsTiles {
+    const void *base5;          // the ksk5 of some member (slot 0's)
+    const int64_t *ksk5_off;    // [n_keys] device: (slot's ksk5 - base5) / 16
+    const int32_t *order;       // [B] device
+    const int32_t *offsets;     // [n_keys + 1] device
+    const KsTile *tiles;        // [ntiles] device
+    int32_t n_keys, ntiles;
+};
+int ks5_tile_lanes();
+// trace name "k_keyswitch_v5(int8-mfma+multi-key[+splitN])"
+hipError_t launch_keyswitch_rows_tiles(const RingKsTiles &t, int B, int nks, const CircKs *ks, const int32_t *u_a,
+                                       const int32_t *u_b, int32_t *wa, int32_t *wb, hipStream_t s);
+// the key switch of one key group of such a level through the single-key kernels: nks outputs x the n
+// instances inst[0 .. n) (device; clamped into [0, B)) of a wire table of stride B; lane t = o n + j
+hipError_t launch_keyswitch_rows_inst(const DeviceKey &key, int B, int nks, const CircKs *ks, const int32_t *inst,
+                                      int n, const int32_t *u_a, const int32_t *u_b, int32_t *wa, int32_t *wb,
+                                      hipStream_t s);
+
 // which key-switch kernel the larger batches take: 5 (int8 MFMA), or 4 with TFHE_AMD_KS5=0
 int ks_version();
 size_t ksk_v4_words();

@@ -13,25 +13,13 @@
 #include <mutex>
 #include <vector>
 
+#include "api_internal.h"
 #include "context.h"
+#include "keyring_internal.h"
 
 using namespace tfhe_amd;
 
-struct TfheAmdKeyRing {
-    std::vector<TfheAmdContext *> m;   // slot -> member (borrowed)
-    int device = -1;
-    void **d_fft = nullptr;            // [n_keys] the members' bk_fft (v6)
-    void **d_v2 = nullptr;             // [n_keys] the members' bk_v2 (v4)
-    std::mutex mu;                     // one call at a time: the tables below are the call's
-    void *h_tab = nullptr, *d_tab = nullptr;   // row tables: pinned host copy, device copy
-    size_t tab_bytes = 0;
-    hipEvent_t up = nullptr;           // the last upload out of h_tab
-    StreamFence fence;                 // d_tab reuse across caller streams
-};
-
 namespace {
-
-constexpr int kRingMaxKeys = 256;
 
 // blind rotations of one gate of the ring's gate forms: 2 (MUX), 1 (binary), 0 (NOT / COPY), -1 (refused)
 int gate_rows(int gate) {
@@ -313,6 +301,7 @@ extern "C" int tfhe_amd_keyring_create(TfheAmdContext *const *ctxs, int n_keys, 
 
 extern "C" int tfhe_amd_keyring_destroy(TfheAmdKeyRing *ring) {
     if (!ring) return TFHE_AMD_OK;
+    tfhe_amd_internal_circuits_forget_context(ring->uid);   // circuits' device state of runs on this ring
     {
         DeviceScope dev_scope(ring->device);
         (void)hipDeviceSynchronize();   // launches on caller streams may still read the tables

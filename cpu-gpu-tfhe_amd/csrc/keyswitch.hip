@@ -57,7 +57,11 @@ struct KsPlain {               // gate batch: u[ct] (+ u2[ct]) + (0, add_b) -> r
     int32_t add_b;
     int32_t *res_a, *res_b;
     int B;
+    static constexpr bool kTiled = false;
     __device__ int count() const { return B; }
+    __device__ bool live(int ct) const { return ct < B; }
+    __device__ const uint4 *key5(const uint4 *w5, int) const { return w5; }
+    __device__ int spare(int) const { return 0; }   // the lane a padding lane loads in its place
     __device__ KsLane lane(int ct) const {
         KsLane l;
         l.ua = u_a + (size_t)ct * kN;
@@ -73,7 +77,11 @@ struct KsRows {                // circuit level: lane ct = g B + k -> wire ks[g]
     const int32_t *u_a, *u_b;
     int32_t *wa, *wb;
     int B, nks;
+    static constexpr bool kTiled = false;
     __device__ int count() const { return B * nks; }
+    __device__ bool live(int ct) const { return ct < B * nks; }
+    __device__ const uint4 *key5(const uint4 *w5, int) const { return w5; }
+    __device__ int spare(int) const { return 0; }   // the lane a padding lane loads in its place
     __device__ KsLane lane(int ct) const {
         const int g = ct / B, k = ct - g * B;
         const CircKs e = ks[g];
@@ -90,6 +98,103 @@ struct KsRows {                // circuit level: lane ct = g B + k -> wire ks[g]
         l.ra = wa + so * kn;
         l.rb = wb + so;
         return l;
+    }
+};
+
+// The lane of output o at instance k of a circuit level (both lane maps below)
+__device__ __forceinline__ KsLane ks_rows_lane(const CircKs e, int B, int k, const int32_t *u_a, const int32_t *u_b,
+                                               int32_t *wa, int32_t *wb) {
+    const size_t s1 = (size_t)e.r1 * B + k, so = (size_t)e.out * B + k;
+    KsLane l;
+    l.ua = u_a + s1 * kN;
+    l.b = (uint32_t)u_b[s1] + (uint32_t)e.add_b;
+    l.ua2 = nullptr;
+    if (e.r2 >= 0) {
+        const size_t s2 = (size_t)e.r2 * B + k;
+        l.ua2 = u_a + s2 * kN;
+        l.b += (uint32_t)u_b[s2];
+    }
+    l.ra = wa + so * kn;
+    l.rb = wb + so;
+    return l;
+}
+__device__ __forceinline__ int ks_clamp(int v, int n) {   // into [0, n), n >= 1
+    v = v < n ? v : n - 1;
+    return v > 0 ? v : 0;
+}
+struct KsRowsInst {            // one key group of a mixed-key circuit level: lane ct = o n + j -> instance inst[j]
+    const CircKs *ks;
+    const int32_t *u_a, *u_b;
+    int32_t *wa, *wb;
+    int B, nks, n;
+    const int32_t *inst;       // [n], entries clamped into [0, B) before they index
+    static constexpr bool kTiled = false;
+    __device__ int count() const { return n * nks; }
+    __device__ bool live(int ct) const { return ct < n * nks; }
+    __device__ const uint4 *key5(const uint4 *w5, int) const { return w5; }
+    __device__ int spare(int) const { return 0; }   // the lane a padding lane loads in its place
+    __device__ KsLane lane(int ct) const {
+        const int o = ct / n, j = ct - o * n;
+        return ks_rows_lane(ks[o], B, ks_clamp(inst[j], B), u_a, u_b, wa, wb);
+    }
+};
+// All key groups of a mixed-key circuit level in one launch (engine.h RingKsTiles): lane index ct =
+// tile M + i over the padded tiles.  Every index read from the tables is clamped before it forms an
+// address: the tile's slot into [0, n_keys), the output into [0, nks), the instance into [0, B).
+template <int M>
+struct KsRingTiles {
+    const CircKs *ks;
+    const int32_t *u_a, *u_b;
+    int32_t *wa, *wb;
+    int B, nks;
+    RingKsTiles t;
+    static constexpr bool kTiled = true;
+    __device__ int count() const { return t.ntiles * M; }
+    // (the lanes of a wave lie in one tile, so the tile index is read from the first active lane: its
+    // record, the group's offsets and everything derived from them stay in scalar registers)
+    __device__ static int tile_of(int ct) { return __builtin_amdgcn_readfirstlane(ct / M); }
+    __device__ bool live(int ct) const {
+        const int mt = tile_of(ct);
+        return mt < t.ntiles && ct - mt * M < t.tiles[mt].live;
+    }
+    // a padding lane loads its tile's first lane, which is always live (and keeps the wave in one tile)
+    __device__ int spare(int ct) const { return ct / M * M; }
+    // the tile's ksk5: the kernel argument (engine.h RingKsTiles base5) moved by the slot's distance,
+    // which is made wave-uniform half by half like the rotation's key (br_common.h ring_key)
+    __device__ const uint4 *key5(const uint4 *w5, int mt) const {
+        const int g = ks_clamp(t.tiles[mt].slot, t.n_keys);
+        const long long d = t.ksk5_off[g];
+        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)d);
+        const int hi = __builtin_amdgcn_readfirstlane((int)(d >> 32));
+        return w5 + (((long long)hi << 32) | lo);
+    }
+    __device__ KsLane lane(int ct) const {
+        const int mt = tile_of(ct);
+        const KsTile tl = t.tiles[mt];
+        const int g = ks_clamp(tl.slot, t.n_keys);
+        const int off = t.offsets[g];
+        int n = t.offsets[g + 1] - off;
+        n = n > 0 ? n : 1;
+        int q0 = tl.first - nks * off;                  // the tile's first lane inside its group
+        q0 = q0 > 0 ? q0 : 0;
+        const int o0 = q0 / n, j0 = q0 - o0 * n;        // uniform: one division per wave
+        // lane q0 + i is output o0 + d at the group's instance r, where j0 + i = d n + r.  j0 + i < n + M,
+        // so d is 0 or 1 for a group of at least M instances; below that j0 + i < 2 M and the quotient
+        // comes from a float product, exact after one correction step at these sizes
+        const int x = j0 + (ct - mt * M);
+        int d, r;
+        if (n >= M) {
+            d = x >= n;
+            r = x - (d ? n : 0);
+        } else {
+            d = (int)((float)x * (1.0f / (float)n));
+            r = x - d * n;
+            if (r >= n) { ++d; r -= n; }
+            if (r < 0) { --d; r += n; }
+        }
+        const int o = ks_clamp(o0 + d, nks);
+        const int k = ks_clamp(t.order[ks_clamp(off + r, B)], B);
+        return ks_rows_lane(ks[o], B, k, u_a, u_b, wa, wb);
     }
 };
 
@@ -209,6 +314,9 @@ constexpr int kKsSmallI = kN / kKsSmallChunks;   // 16 key indices per workgroup
 
 template <class P>
 __global__ __launch_bounds__(512) void k_keyswitch_small_init(P io) {
+    if constexpr (P::kTiled) {   // one workgroup per lane of the padded tiles: the padding has no row
+        if (!io.live(blockIdx.x)) return;
+    }
     const KsLane ln = io.lane(blockIdx.x);
     const int col = threadIdx.x;
     if (col < kn) ln.ra[col] = 0;
@@ -313,7 +421,7 @@ __global__ __launch_bounds__(kKs5Threads) void k_keyswitch_v5(const uint4 *__res
     static_assert(kKs5Threads * kPer == kM * kKs5Ch, "loader mapping");
     const int lct = (tid * MS) >> 1, lpart = MS == 1 ? (tid & 1) : 0;
     const int lg = mt * kM + lct;
-    const KsLane lln = io.lane(lg < io.count() ? lg : 0);
+    const KsLane lln = io.lane(io.live(lg) ? lg : io.spare(lg));
     const uint4 *pa = reinterpret_cast<const uint4 *>(lln.ua) + kU4 * lpart;
     const uint4 *pa2 = reinterpret_cast<const uint4 *>(lln.ua2 ? lln.ua2 : lln.ua) + kU4 * lpart;
     const uint32_t m2 = lln.ua2 ? 0xffffffffu : 0u;   // no second sample: add it masked to 0
@@ -343,7 +451,7 @@ __global__ __launch_bounds__(kKs5Threads) void k_keyswitch_v5(const uint4 *__res
             *reinterpret_cast<uint4 *>(&dg[buf][1][lct][0]) = make_uint4(lo[0], lo[1], lo[2 % kU4], lo[3 % kU4]);
         }
     };
-    const uint4 *src = w5 + ((size_t)nb * kN + (size_t)c0 * kKs5Ch) * 64 + tid;
+    const uint4 *src = io.key5(w5, mt) + ((size_t)nb * kN + (size_t)c0 * kKs5Ch) * 64 + tid;
     uint4 p[kKs5Pieces];
 #pragma unroll
     for (int q = 0; q < kKs5Pieces; ++q) p[q] = src[q * kKs5Threads];
@@ -420,7 +528,7 @@ __global__ __launch_bounds__(kKs5Threads) void k_keyswitch_v5(const uint4 *__res
             v += (uint32_t)__shfl_xor((int)v, 1, 64);
             v += (uint32_t)__shfl_xor((int)v, 2, 64);
             const int ctm = mt * kM + wave * 32 * MS + 32 * m + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
-            if ((l & 3) == 0 && ctm < io.count() && col <= kn) {
+            if ((l & 3) == 0 && io.live(ctm) && col <= kn) {
                 const KsLane lm = io.lane(ctm);
                 if (SPLIT > 1) atomicAdd(reinterpret_cast<unsigned int *>(col < kn ? lm.ra + col : lm.rb), 0u - v);
                 else if (col < kn) lm.ra[col] = (int32_t)(0u - v);
@@ -554,6 +662,58 @@ hipError_t launch_keyswitch_rows(const DeviceKey &key, int B, int nks, const Cir
     }
     const int groups = (int)(((size_t)B * nks + kKs4Threads - 1) / kKs4Threads);
     launch_ks4(key, groups, B * nks, io, s);
+    return hipGetLastError();
+}
+
+// one key group of a mixed-key circuit level: the kernel choice of launch_keyswitch_rows over the
+// group's nks n lanes
+hipError_t launch_keyswitch_rows_inst(const DeviceKey &key, int B, int nks, const CircKs *ks, const int32_t *inst,
+                                      int n, const int32_t *u_a, const int32_t *u_b, int32_t *wa, int32_t *wb,
+                                      hipStream_t s) {
+    if (B <= 0 || nks <= 0 || n <= 0) return hipSuccess;
+    if (!inst || n > B) return hipErrorInvalidValue;
+    KsRowsInst io{ks, u_a, u_b, wa, wb, B, nks, n, inst};
+    const long count = (long)n * nks;
+    if (count <= ks_small_max()) {
+        trace_kernel("k_keyswitch_small");
+        hipLaunchKernelGGL(k_keyswitch_small_init<KsRowsInst>, dim3((unsigned)count), dim3(512), 0, s, io);
+        if (count <= ks_unroll_max())
+            hipLaunchKernelGGL((k_keyswitch_small<KsRowsInst, kKsSmallI>), dim3(kKsSmallChunks, (unsigned)count), dim3(512),
+                               0, s, key.ksk, io);
+        else
+            hipLaunchKernelGGL((k_keyswitch_small<KsRowsInst, kKsSmallU>), dim3(kKsSmallChunks, (unsigned)count), dim3(512),
+                               0, s, key.ksk, io);
+        return hipGetLastError();
+    }
+    const int groups = (int)(((size_t)count + kKs4Threads - 1) / kKs4Threads);
+    launch_ks4(key, groups, (int)count, io, s);
+    return hipGetLastError();
+}
+
+// all key groups of a mixed-key circuit level: ks-v5 over the level's M-tiles, the split forms as
+// over a batch of as many M-tiles (the init kernel runs one workgroup per lane of the padded tiles)
+int ks5_tile_lanes() { return 32 * kKs5Waves; }
+hipError_t launch_keyswitch_rows_tiles(const RingKsTiles &t, int B, int nks, const CircKs *ks, const int32_t *u_a,
+                                       const int32_t *u_b, int32_t *wa, int32_t *wb, hipStream_t s) {
+    if (B <= 0 || nks <= 0 || t.ntiles <= 0) return hipSuccess;
+    if (!t.base5 || !t.ksk5_off || !t.order || !t.offsets || !t.tiles || t.n_keys < 1) return hipErrorInvalidValue;
+    constexpr int M = 32 * kKs5Waves;
+    using P = KsRingTiles<M>;
+    const P io{ks, u_a, u_b, wa, wb, B, nks, t};
+    const int split = ks5_split(t.ntiles);
+    if (split > 1) hipLaunchKernelGGL(k_keyswitch_small_init<P>, dim3((unsigned)t.ntiles * M), dim3(512), 0, s, io);
+    const dim3 grid((unsigned)t.ntiles * kKs5Nb * split);
+    trace_kernel(split == 8   ? "k_keyswitch_v5(int8-mfma+multi-key+split8)"
+                 : split == 4 ? "k_keyswitch_v5(int8-mfma+multi-key+split4)"
+                 : split == 2 ? "k_keyswitch_v5(int8-mfma+multi-key+split2)"
+                              : "k_keyswitch_v5(int8-mfma+multi-key)");
+    const uint4 *w5 = static_cast<const uint4 *>(t.base5);   // each tile moves it to its slot's key (KsRingTiles::key5)
+    switch (split) {
+    case 8: hipLaunchKernelGGL((k_keyswitch_v5<P, 8, 1>), grid, dim3(kKs5Threads), 0, s, w5, io); break;
+    case 4: hipLaunchKernelGGL((k_keyswitch_v5<P, 4, 1>), grid, dim3(kKs5Threads), 0, s, w5, io); break;
+    case 2: hipLaunchKernelGGL((k_keyswitch_v5<P, 2, 1>), grid, dim3(kKs5Threads), 0, s, w5, io); break;
+    default: hipLaunchKernelGGL((k_keyswitch_v5<P, 1, 1>), grid, dim3(kKs5Threads), 0, s, w5, io); break;
+    }
     return hipGetLastError();
 }
 

@@ -2056,3 +2056,67 @@ class KeyRing:
             self.h, B, _ip(k), tv.shape[0], tv.data_ptr(), None if lut_index is None else lut_index.data_ptr(),
             res_a.data_ptr(), res_b.data_ptr(), x_a.data_ptr(), x_b.data_ptr(), stream),
             "keyring_bootstrap_lut_batch_dev")
+
+    # ---- mixed-key circuits
+
+    @staticmethod
+    def circuit_tile():
+        """the tile size (lanes) of the engine's one-launch key switch over key groups"""
+        return lib.tfhe_amd_keyring_circuit_tile()
+
+    @staticmethod
+    def circuit_plan_of(n_keys, key_of, nks, tile=None):
+        """tfhe_amd_keyring_circuit_plan -> (order [B], offsets [n_keys + 1], tiles [n_tiles][3] = slot,
+        first lane, live lanes) of a level with nks key-switched outputs; needs no GPU"""
+        k = np.ascontiguousarray(key_of, dtype=np.int32); B = k.shape[0]
+        tile = KeyRing.circuit_tile() if tile is None else int(tile)
+        order = np.zeros(B, np.int32); offsets = np.zeros(max(int(n_keys), 0) + 1, np.int32); nt = ctypes.c_int()
+        _check(lib.tfhe_amd_keyring_circuit_plan(B, int(n_keys), _ip(k), int(nks), tile, None, None, None, 0,
+                                                 ctypes.byref(nt)), "tfhe_amd_keyring_circuit_plan")
+        tiles = np.zeros((nt.value, 3), np.int32)
+        _check(lib.tfhe_amd_keyring_circuit_plan(B, int(n_keys), _ip(k), int(nks), tile, _ip(order), _ip(offsets),
+                                                 _ip(tiles), nt.value, None), "tfhe_amd_keyring_circuit_plan")
+        return order, offsets, tiles
+
+    def circuit_plan(self, key_of, nks, tile=None):
+        return self.circuit_plan_of(len(self), key_of, nks, tile)
+
+    def circuit_dev(self, circ, key_of, wa, wb, stream=None):
+        """tfhe_amd_keyring_circuit_run_dev on torch tensors: wa [n_wires][B][500], wb [n_wires][B] with the
+        input wires filled, instance k under key slot key_of[k] (host sequence).  Enqueued."""
+        k = np.ascontiguousarray(key_of, dtype=np.int32)
+        if k.ndim != 1:
+            raise TfheAmdError(f"key_of: need one key slot per instance, got shape {k.shape}")
+        B = k.shape[0]
+        n_w = circ.info()["wires"]
+        if B > 0:
+            self._dev_check(wa, (n_w, B, n_lwe), "wa")
+            self._dev_check(wb, (n_w, B), "wb")
+        ptr = (lambda t: None if t is None or B == 0 else t.data_ptr())
+        _check(lib.tfhe_amd_keyring_circuit_run_dev(self.h, circ.h, B, _ip(k), ptr(wa), ptr(wb), stream),
+               "keyring_circuit_run_dev")
+
+    def circuit_host(self, circ, key_of, in_wires, in_a, in_b, out_wires):
+        """tfhe_amd_keyring_circuit_run_host: in_a [n_in][B][500], in_b [n_in][B] for the wires in_wires ->
+        (out_a [n_out][B][500], out_b [n_out][B]); synchronous"""
+        k = np.ascontiguousarray(key_of, dtype=np.int32)
+        if k.ndim != 1:
+            raise TfheAmdError(f"key_of: need one key slot per instance, got shape {k.shape}")
+        B = k.shape[0]
+        in_a = i32(in_a); in_b = i32(in_b)
+        n_in, n_out = len(in_wires), len(out_wires)
+        if in_a.shape != (n_in, B, n_lwe) or in_b.shape != (n_in, B):
+            raise TfheAmdError(f"inputs: need [{n_in}][{B}][500] / [{n_in}][{B}], got {in_a.shape} / {in_b.shape}")
+        out_a = np.zeros((n_out, B, n_lwe), np.int32); out_b = np.zeros((n_out, B), np.int32)
+        _check(lib.tfhe_amd_keyring_circuit_run_host(self.h, circ.h, B, _ip(k), n_in, _ids(in_wires), _p(in_a), _p(in_b),
+                                                     n_out, _ids(out_wires), _p(out_a), _p(out_b)),
+               "keyring_circuit_run_host")
+        return out_a, out_b
+
+
+lib.tfhe_amd_keyring_circuit_plan.argtypes = [ctypes.c_int, ctypes.c_int, _IP, ctypes.c_int, ctypes.c_int, _IP, _IP, _IP,
+                                              ctypes.c_int, _IP]
+lib.tfhe_amd_keyring_circuit_tile.argtypes = []
+lib.tfhe_amd_keyring_circuit_run_dev.argtypes = [_VP, _VP, ctypes.c_int, _IP, _VP, _VP, _VP]
+lib.tfhe_amd_keyring_circuit_run_host.argtypes = [_VP, _VP, ctypes.c_int, _IP, ctypes.c_int, _IP, _I32P, _I32P,
+                                                  ctypes.c_int, _IP, _I32P, _I32P]

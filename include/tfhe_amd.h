@@ -1064,6 +1064,41 @@ int tfhe_amd_keyring_bootstrap_lut_batch_host(TfheAmdKeyRing *ring, int B, const
                                               int32_t *res_a, int32_t *res_b,
                                               const int32_t *x_a, const int32_t *x_b);
 
+/* ---- Mixed-key circuits.  One run of a circuit over B instances, instance k under
+ * the cloud key of ring slot key_of[k] (HOST array, any order).  Every level takes one blind-rotation
+ * launch chain and one guard launch over all rows x instances, each instance under its own
+ * bootstrapping key, one key-switch launch over all key groups (one launch per non-empty group when
+ * a member lacks the int8 key layout, TFHE_AMD_KS5=0, or the instances are of one slot), and the
+ * key-independent linear launch.  Every word of every wire equals what tfhe_amd_circuit_run_dev on
+ * the slot's own context writes for that slot's instances.  The run executes in member 0's frame like
+ * every ring call; the circuit keeps its level tables and scratch for the ring until the ring is
+ * destroyed or the circuit recompiled.
+ * wires_a [n_wires][B][500], wires_b [n_wires][B] on the ring's device, input wires filled; enqueued
+ * on `stream` (NULL: member 0's), returns without waiting.  TFHE_AMD_E_ARG, before anything is
+ * launched or written, for a NULL ring, circuit or key_of, B < 0, a slot outside the ring, NULL wire
+ * arrays with B > 0, and a circuit that holds a select node (packing keys are per key); B = 0 is
+ * TFHE_AMD_OK with no launch. */
+int tfhe_amd_keyring_circuit_run_dev(TfheAmdKeyRing *ring, TfheAmdCircuit *circ, int B, const int *key_of,
+                                     int32_t *wires_a, int32_t *wires_b, void *stream);
+/* The same from host memory, synchronous, in the shape of tfhe_amd_multi_circuit_run_host: in_a
+ * [n_in][B][500], in_b [n_in][B] hold the input wires in_wires[k]; the wires out_wires[k] come back
+ * in out_a [n_out][B][500], out_b [n_out][B]. */
+int tfhe_amd_keyring_circuit_run_host(TfheAmdKeyRing *ring, TfheAmdCircuit *circ, int B, const int *key_of,
+                                      int n_in, const int *in_wires, const int32_t *in_a, const int32_t *in_b,
+                                      int n_out, const int *out_wires, int32_t *out_a, int32_t *out_b);
+/* The order and the key-switch tiles of such a run (pure host function).  order [B] = the instances
+ * sorted by slot, stable; offsets [n_keys + 1] = where each slot's group starts in `order`.  A level
+ * with nks key-switched outputs has the lanes nks offsets[g] + o n_g + j of group g (n_g instances):
+ * output o at the group's j-th instance.  They are cut into tiles of `tile` lanes that never span two
+ * groups; tile t is tiles[3 t .. 3 t + 2] = its slot, its first lane, its live lanes (1 .. tile).
+ * *n_tiles = their number; tiles == NULL counts only, else more than tile_cap tiles is TFHE_AMD_E_ARG.
+ * Any output may be NULL.  TFHE_AMD_E_ARG also for B < 0, n_keys outside [1, 256], nks < 0, tile < 1,
+ * a slot outside [0, n_keys) and nks B above 2^30 - 1.  tfhe_amd_keyring_circuit_tile: the tile size
+ * the engine's key switch uses. */
+int tfhe_amd_keyring_circuit_plan(int B, int n_keys, const int *key_of, int nks, int tile,
+                                  int *order, int *offsets, int *tiles, int tile_cap, int *n_tiles);
+int tfhe_amd_keyring_circuit_tile(void);
+
 #ifdef __cplusplus
 }
 #endif
